@@ -2,8 +2,14 @@
 """bench.py -- genomes/sec of the MUM + LCB hot path (phases A-D of parsnp_core: anchor multi-MUM search,
 recursive inter-anchor extension, LCB formation) on MI355X, on BASELINE.json's headline configuration.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload bact200] [--genomes G]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload bact200] [--genomes G] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the JSON line.  --full adds what takes runs of its own or work
+outside the steps: the CPU baseline, BASELINE's other single-GPU configurations (`other_configs`), for N > 1 the sharded
+measurement (`sharded_strong`), and the rows of the MUM list fetched and the XMFA written after the steps (`materialize_ms`,
+`split_s.output`, `cold.wall_s`).  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (see
+dump_outputs); the inputs are generated from fixed seeds, so two builds can be compared output for output.
 
 One "step" = one pass of the hot path over one batch of synthetic genomes (reference + G queries) whose packed
 sequences are already resident in HBM (ingest, upload and XMFA writing are outside the timed region and reported
@@ -138,6 +144,55 @@ def cpu_baseline(workdir, rp, qs, sample_queries):
                       "1-s log timers = %.0f s, whole process %.1f s; host has %d cores" % (what, sample_queries, path_s, wall, os.cpu_count())}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def xmfa_records(path):
+    """one row per record of an XMFA: (LCB number, sequence index, start, end, strand +1/-1, aligned columns, MUM columns).
+    MUM columns are the lower-case ones (output.cpp), so the last column pins the MUM bases and the coordinates the LCBs."""
+    import numpy as np
+    data = np.fromfile(path, dtype=np.uint8)
+    nl = np.flatnonzero(data == ord("\n"))
+    starts = np.concatenate(([0], nl[:-1] + 1))
+    first = data[starts]
+    mark = np.flatnonzero((first == ord(">")) | (first == ord("=")))      # record headers and LCB ends, in file order
+    hdr = mark[first[mark] == ord(">")]
+    ends = np.append(mark, len(starts))
+    nxt = ends[np.searchsorted(mark, hdr, side="right")]                 # the line that ends each record ('>', '=' or end of file)
+    a = nl[hdr] + 1                  # first byte of the record's sequence lines
+    b = np.append(starts, len(data))[nxt]                                # first byte of the line after them
+    lines = nxt - hdr - 1
+    cols = (b - a) - lines           # bytes less one newline per sequence line
+    lower = ((data >= ord("a")) & (data <= ord("z"))).view(np.uint8)
+    idx = np.stack([a, b], axis=1).ravel()
+    mum = np.add.reduceat(lower, np.minimum(idx, len(data) - 1), dtype=np.int64)[0::2]
+    mum[a >= b] = 0
+    lcb = np.cumsum(first[mark] == ord("="))[np.searchsorted(mark, hdr)]     # '=' lines before the header
+    pat = re.compile(rb">\s*(\d+):(\d+)-(\d+)\s+([+-])")
+    rows = np.empty((len(hdr), 7), np.float64)
+    for i, h in enumerate(hdr):
+        m = pat.match(data[starts[h]:nl[h]].tobytes())
+        rows[i, :5] = (lcb[i], int(m.group(1)), int(m.group(2)), int(m.group(3)), 1 if m.group(4) == b"+" else -1)
+    rows[:, 5] = cols
+    rows[:, 6] = mum
+    return rows
+
+
+def dump_outputs(ddir, rep, xmfa):
+    """what the last timed step computed, as float64 .npy files: `step_counts` (anchors, MUMs, LCBs, core bases aligned) and
+    `xmfa_records` (xmfa_records() over the XMFA written from that step); above DUMP_MAX_BYTES in all, a fixed seeded sample of
+    the records, in file order"""
+    import numpy as np
+    os.makedirs(ddir, exist_ok=True)
+    counts = np.array([rep["anchors"], rep["mums"], rep["lcbs"], rep["core_bp"]], np.float64)
+    rows = xmfa_records(xmfa)
+    cap = (DUMP_MAX_BYTES - counts.nbytes - 4096) // rows.itemsize // rows.shape[1]
+    if len(rows) > cap:
+        rows = rows[np.sort(np.random.default_rng(0).choice(len(rows), cap, replace=False))]
+    np.save(os.path.join(ddir, "step_counts.npy"), counts)
+    np.save(os.path.join(ddir, "xmfa_records.npy"), rows)
+
+
 def usable_cpus():
     """CPUs this process may use: affinity mask, capped by the cgroup CPU quota (cpu.max) where there is one"""
     n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
@@ -219,16 +274,23 @@ def main():
                     help="N > 1: 'partition' = one independent partition per GPU, weak scaling, no data-path collective (the headline "
                          "value); 'sharded' = ONE alignment (the workload's genomes) sharded over the GPUs, strong scaling, both exchanges "
                          "of every engine call over the engine's own RCCL communicator (device buffers); 'both' (default) = the partition "
-                         "measurement as the line's value and, for N > 1, the sharded measurement of the same workload beside it "
+                         "measurement as the line's value and, for N > 1 with --full, the sharded measurement of the same workload beside it "
                          "(`sharded_strong`, run by one child process per rank so that it cannot take the headline down with it)")
     ap.add_argument("--inputs", default="", help="directory with ref.fna + g*.fna to use instead of generating the workload (the sharded child of --mode both)")
     ap.add_argument("--tune", action="append", default=[], metavar="KEY=VALUE",
                     help="a tunable of the engine session (pm_session_tune: group_small=0, ...) for before/after measurements; named in config.tune")
     ap.add_argument("--other-configs", default="auto", choices=["auto", "on", "off"],
                     help="ms per step of BASELINE's other single-GPU configurations (viral50 = config 2, rearr500 = config 5) and of config 3 with ten inverted segments (bact200inv) in the line's "
-                         "`other_configs`, each measured by a child run of this script; auto = on for the default workload at N = 1")
+                         "`other_configs`, each measured by a child run of this script; auto = on for the default workload at N = 1 with --full")
     ap.add_argument("--keep", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what a plain run leaves out: CPU baseline (--cpu-sample), other configurations (--other-configs auto), "
+                         "the sharded measurement beside N > 1 (--mode both), the fetch of the MUM rows and the XMFA writing after the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # OpenMP workers between the short parallel host phases (~20 per step): the GPU boxes cap the CPU time of the container
     # (cgroup quota), and workers that spin without bound burn it (measured in round 1: "active" cost 50 % of the throughput);
@@ -255,7 +317,7 @@ def main():
     tdev = "cuda"
     sharded = args.mode == "sharded"
     # (PARSNP_BENCH_CHILD_TEST=1: exercise the child-process plumbing of `both` with the one rank a single-GPU box allows)
-    both = args.mode == "both" and (world > 1 or os.environ.get("PARSNP_BENCH_CHILD_TEST") == "1")
+    both = args.full and args.mode == "both" and (world > 1 or os.environ.get("PARSNP_BENCH_CHILD_TEST") == "1")
     if world > 1:
         import torch.distributed as dist
         if torch.cuda.device_count() >= world and not sharded:
@@ -367,15 +429,17 @@ def main():
             barrier()
             # the timed region ends with the MUM list, the LCBs and their counters on the host; the ROWS of the MUMs stay on the device
             # until the writer asks (resident route).  What fetching them costs is measured here, once, and reported beside ms_per_step
+            # (--full; the XMFA is also written for --dump-outputs, whose records are read from it)
             materialize_ms = None
-            if rank == 0 and not sharded:
+            if rank == 0 and not sharded and args.full:
                 run.L.pc_materialize.argtypes = [__import__("ctypes").c_void_p]
                 run.L.pc_materialize.restype = __import__("ctypes").c_double
                 materialize_ms = round(float(run.L.pc_materialize(run.h)), 3)
-            t_out = time.time()
-            if rank == 0:
+            output_s = None
+            if rank == 0 and (args.full or args.dump_outputs):
+                t_out = time.time()
                 run.write()          # XMFA + log of one partition: outside the timed region, reported as split_s.output
-            output_s = time.time() - t_out
+                output_s = time.time() - t_out
             # how many ranks RCCL itself counts: the engine's communicator (sharded), torch's (partition mode's interval exchange)
             if sharded:
                 run.L.pc_rccl_ranks.argtypes = [__import__("ctypes").c_void_p]
@@ -583,7 +647,7 @@ def main():
             ms_per_step = 1e3 * elapsed / args.steps
             # BASELINE's other single-GPU configurations, a child run each (their own process: nothing of them is resident here)
             other = None
-            want_other = args.other_configs == "on" or (args.other_configs == "auto" and args.workload == "bact200" and not args.genomes and world == 1 and not args.inputs)
+            want_other = args.other_configs == "on" or (args.other_configs == "auto" and args.full and args.workload == "bact200" and not args.genomes and world == 1 and not args.inputs)
             if want_other:
                 other = {}
                 for wl, st in (("viral50", 20), ("bact200inv", 20), ("rearr500", 3)):
@@ -635,8 +699,8 @@ def main():
                 "cold": None if cold_step_s is None else {
                     # one whole process, nothing resident: FASTA ingest + upload/packing + the first pass + XMFA/log writing
                     "cold_step_s": round(cold_step_s, 4),
-                    "wall_s": round(rep["ingest_s"] + rep["upload_s"] + cold_step_s + output_s, 4),
-                    "cold_wall_genomes_per_s": round(G / (rep["ingest_s"] + rep["upload_s"] + cold_step_s + output_s), 2)},
+                    "wall_s": None if output_s is None else round(rep["ingest_s"] + rep["upload_s"] + cold_step_s + output_s, 4),
+                    "cold_wall_genomes_per_s": None if output_s is None else round(G / (rep["ingest_s"] + rep["upload_s"] + cold_step_s + output_s), 2)},
                 "host_split_s": rep.get("host_split_s"),
                 "engine_ms": {k: round(v, 3) for k, v in rep["engine_ms"].items()},
                 "anchor_launch_ms": {k: round(v, 3) for k, v in phases.items()},
@@ -644,8 +708,13 @@ def main():
                             "speculative_rounds": rep["spec_rounds"]},
                 "roofline": roof,
                 "build": {"so_sha256": so_sha256(), "engine_src_sha256": engine_src_sha256()},      # what ran: profiles/<round>/*.json carry the same stamps
-                "cpu_baseline": cpu_baseline(workdir, rp, qs, args.cpu_sample) if (args.cpu_sample > 0 and world == 1) else None,
+                "cpu_baseline": cpu_baseline(workdir, rp, qs, args.cpu_sample) if (args.full and args.cpu_sample > 0 and world == 1) else None,
             }
+            if args.dump_outputs:
+                xmfa = [f for f in os.listdir(out) if f.endswith(".xmfa")]
+                if len(xmfa) != 1:
+                    raise SystemExit("bench.py --dump-outputs: expected one XMFA in the output directory, found %s" % xmfa)
+                dump_outputs(args.dump_outputs, rep, os.path.join(out, xmfa[0]))
             print(json.dumps(line))
         if dist is not None:
             dist.barrier()

@@ -1,11 +1,13 @@
 """Seeded inputs for the gap-aligner parity tests: sets of diverged copies of a short sequence, the shape of the gaps
 between adjacent MUMs that the XMFA writer aligns (reference: src/parsnp.cpp:790-865)."""
+import hashlib
 import os
 import random
 import subprocess
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MUSCLE_REF = os.path.join(ROOT, "oracle", "_ref", "muscle_ref")
+MUSCLE_GOLDEN = os.path.join(ROOT, "tests", "golden", "muscle_runs.json.xz")
 
 
 def mutate(rng, s, rate, alpha="ACGT"):
@@ -65,6 +67,11 @@ def golden_blocks():
 
 
 def reference_align(blks):
+    """the reference's MuscleInterface on every block (oracle/_ref/muscle_ref), from its record in tests/golden/muscle_runs.json.xz"""
+    import refruns
     inp = "\n\n".join("\n".join(b) for b in blks) + "\n"
-    out = subprocess.run([MUSCLE_REF], input=inp.encode(), capture_output=True, check=True).stdout.decode()
-    return [b.split("\n") for b in out.strip("\n").split("\n\n")]
+
+    def compute():
+        out = subprocess.run([MUSCLE_REF], input=inp.encode(), capture_output=True, check=True).stdout.decode()
+        return [b.split("\n") for b in out.strip("\n").split("\n\n")]
+    return refruns.recorded(MUSCLE_GOLDEN, hashlib.sha256(inp.encode()).hexdigest(), MUSCLE_REF, compute)

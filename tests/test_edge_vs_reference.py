@@ -9,12 +9,12 @@ import numpy as np
 import pytest
 
 import oracles
+import refruns
 import xmfa_util
 from parsnp_amd import driver, synth
 from parsnp_amd.paths import CORE_BIN
 
-REFBIN = os.path.join(oracles.REFDIR, "parsnp_core_ref")
-pytestmark = pytest.mark.skipif(not os.path.exists(REFBIN), reason="reference binary not built/shipped")
+REFBIN = refruns.REFBIN
 
 
 def cases():
@@ -79,8 +79,8 @@ def run(core, rp, qs, out, kw):
 def side_by_side(core, name, tmp_path):
     ref, gs, kw = CASES[name]
     rp, qs = synth.write_set(str(tmp_path / "in"), ref, gs)
-    a = run(REFBIN, rp, qs, str(tmp_path / "ref"), kw)
-    b = run(core, rp, qs, str(tmp_path / "mine"), kw)
+    a = refruns.reference(run, rp, qs, str(tmp_path / "ref"), kw)
+    b = refruns.normal(run(core, rp, qs, str(tmp_path / "mine"), kw))
     assert a == b
     assert a[0] == 0
     if name == "unaligned_out":

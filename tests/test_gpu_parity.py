@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import oracles
+import refruns
 import test_emu_engine as T
 import test_host_logic
 import xmfa_util
@@ -348,20 +349,26 @@ def test_parsnp_core_harsh_inputs(libs, tmp_path, name):
     assert xmfa_util.log_counters(os.path.join(out, "parsnpAligner.log")) == want["log"]
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(oracles.REFDIR, "parsnp_core_ref")), reason="reference binary not shipped")
+def core_run(core, rp, qs, out):
+    """-> exit code, MUM/LCB signature, md5 of the XMFA, log counters"""
+    rc, _ = driver.run_core(core, rp, qs, out)
+    x = os.path.join(out, "parsnpAligner.xmfa")
+    if not os.path.exists(x):
+        return rc, None, None, None
+    return rc, xmfa_util.mum_lcb_signature(x), xmfa_util.md5(x), xmfa_util.log_counters(os.path.join(out, "parsnpAligner.log"))
+
+
 def test_parsnp_core_vs_reference_binary_fresh_input(libs, tmp_path):
-    """an input that has no committed golden: run the shipped reference binary and the product side by side"""
+    """an input that has no other committed golden: the reference binary's recorded result (tests/refruns.py) and the product side by side"""
     r, gs = synth.population(seed=77, n=400_000, n_genomes=9, div=0.02, indel_frac=0.05)
     g = gs[4]; gs[4] = g[:100_000] + oracles.revcomp(g[100_000:140_000]) + g[140_000:]
     rp, qs = synth.write_set(str(tmp_path / "in"), r, gs)
-    ref_bin = os.path.join(oracles.REFDIR, "parsnp_core_ref")
-    rc1, _ = driver.run_core(ref_bin, rp, qs, str(tmp_path / "ref"))
-    rc2, _ = driver.run_core(CORE_BIN, rp, qs, str(tmp_path / "hip"))
-    assert rc1 == 0 and rc2 == 0
-    a, b = str(tmp_path / "ref" / "parsnpAligner.xmfa"), str(tmp_path / "hip" / "parsnpAligner.xmfa")
-    assert xmfa_util.mum_lcb_signature(a) == xmfa_util.mum_lcb_signature(b)
-    assert xmfa_util.md5(a) == xmfa_util.md5(b)
-    assert xmfa_util.log_counters(str(tmp_path / "ref" / "parsnpAligner.log")) == xmfa_util.log_counters(str(tmp_path / "hip" / "parsnpAligner.log"))
+    a = refruns.reference(core_run, rp, qs, str(tmp_path / "ref"))
+    b = refruns.normal(core_run(CORE_BIN, rp, qs, str(tmp_path / "hip")))
+    assert a[0] == 0 and b[0] == 0
+    assert a[1] == b[1]
+    assert a[2] == b[2]
+    assert a[3] == b[3]
 
 
 def test_bench_two_ranks_smoke(libs, tmp_path):
@@ -399,7 +406,7 @@ def test_bench_both_scalings_child_process(libs):
     exercised with one rank (PARSNP_BENCH_CHILD_TEST): the child's line comes back under `sharded_strong`, where the engine's RCCL communicator counts 1 rank"""
     import subprocess, sys
     from conftest import ROOT
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", "pop6x200k", "--cpu-sample", "0"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", "pop6x200k", "--cpu-sample", "0", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=dict(os.environ, PARSNP_BENCH_CHILD_TEST="1"))
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
@@ -516,7 +523,7 @@ def test_bench_two_gpus_both_scalings(libs):
     assert one.returncode == 0, one.stderr[-3000:]
     d1 = json.loads([l for l in one.stdout.splitlines() if l.startswith("{")][-1])
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1", "--master-port", "29541",
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "2", "--cpu-sample", "0"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "2", "--cpu-sample", "0", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])

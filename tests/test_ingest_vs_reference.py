@@ -10,11 +10,11 @@ import numpy as np
 import pytest
 
 import oracles
+import refruns
 import xmfa_util
 from parsnp_amd import driver, synth
 
-REFBIN = os.path.join(oracles.REFDIR, "parsnp_core_ref")
-pytestmark = pytest.mark.skipif(not os.path.exists(REFBIN), reason="reference binary not built/shipped")
+REFBIN = refruns.REFBIN
 
 
 def fasta(seq, width=80, nl="\n", hdr=">s", tail=True, lower=False, blank_every=0, spaces=False, contigs=None):
@@ -76,7 +76,7 @@ def test_fasta_format_vs_reference(cpu_checkers, tmp_path, fmt, who):
         p = str(tmp_path / "in" / ("g%d.fna" % i))
         open(p, "wb").write(fasta(s, **(FORMATS[fmt] if odd else {})))
         paths.append(p)
-    a = run(REFBIN, paths[0], paths[1:], str(tmp_path / "ref"))
-    b = run(cpu_checkers, paths[0], paths[1:], str(tmp_path / "mine"))
+    a = refruns.reference(run, paths[0], paths[1:], str(tmp_path / "ref"))
+    b = refruns.normal(run(cpu_checkers, paths[0], paths[1:], str(tmp_path / "mine")))
     assert a == b
     assert a[0] == 0
