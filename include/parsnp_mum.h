@@ -23,7 +23,8 @@ extern "C" {
 #define PM_EINVAL (-2)   /* bad argument */
 #define PM_ENOMEM (-3)   /* host or device allocation failed */
 #define PM_EHIP (-4)     /* a HIP call or kernel failed */
-#define PM_ELIMIT (-5)   /* a size limit of the engine was exceeded (see pm_limits) */
+#define PM_ELIMIT (-5)   /* a hard size limit of the engine was exceeded: a region of 2^31 bases or more, a batch too large for
+                            64-bit event keys or 2^31 work units (repeat structure is no such limit: see "work_budget") */
 #define PM_EAGAIN (-6)   /* the resident route (pm_store_*) does not apply to this input: the caller takes the host route */
 
 typedef struct pm_session pm_session; /* genomes resident in HBM (2-bit + N-mask, both strands) */
@@ -131,8 +132,12 @@ int pm_result_dirty_known(const pm_result* r);
  * session's ANCHOR TABLE; pm_result_table_id() names it (0: this result left no table).  The resident route below works on it. */
 int64_t pm_result_table_id(const pm_result* r);
 /* Tunables of a session (tests lower the thresholds of the long-list routes so that small inputs take them):
- *   "work_budget"  per-thread step budget of the index walks (default 2^22; a batch that exhausts it is repeated once with
- *                  256 times as much, then PM_ELIMIT)
+ *   "work_budget"  per-thread step budget of the index walks (default 2^22): the threshold at which a region switches to the
+ *                  suffix-array path.  A batch in which a walk exhausts it is run again, and the regions whose walks ran out
+ *                  (tandem repeats of period > 1 with thousands of copies) get rep' and their events from a suffix array of the
+ *                  region instead (cost independent of the copy number); every other region walks as before.  Not an error
+ *   "dense_all"    != 0: every region of every batch takes the suffix-array path from the start (tests compare it with the walks;
+ *                  default 0; the same result)
  *   "dirty_min"    shortest one-region candidate list that gets the overlap / order flags and stays on the device as the
  *                  anchor table (default 4096)
  *   "flagged_div"  pm_store_settle takes an anchor table of which at most one row in flagged_div is flagged (overlaps an earlier
@@ -332,7 +337,11 @@ int pm_gap_align_groups(int device, int64_t n_jobs, const int32_t* n_seqs, const
 const char* pm_gap_last_error(void);
 
 /* Device-side timing of the last pm_multi_mum_batch on this session (HIP events on the engine's stream):
- * names[i] / ms[i] for i < *count (count in: capacity, out: filled).  Used by bench.py's roofline line. */
+ * names[i] / ms[i] for i < *count (count in: capacity, out: filled).  Used by bench.py's roofline line.
+ * A call that took the suffix-array path (see "work_budget") also reports the counts "dense_regions" (regions on the path) and
+ * "dense_rounds" (prefix-doubling rounds of its sort), the phases "dense_sa" (suffix array + rep') and "dense_search" (its
+ * events), and "dense_overrun" (wall ms of the pass that ran out of budget before it; not with "dense_all").  Other calls
+ * report none of these keys. */
 int pm_last_timing(const pm_session* s, int* count, const char** names, float* ms);
 
 #ifdef __cplusplus

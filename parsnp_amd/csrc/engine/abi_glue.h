@@ -312,6 +312,11 @@ int pm_last_timing(const pm_session* cs, int* count, const char** names, float* 
     if (s->call_wall_ms > 0) s->timing.push_back(pm::PhaseTime{"call_wall", s->call_wall_ms});
     if (s->engine->budget_retries) s->timing.push_back(pm::PhaseTime{"budget_retries", (float)s->engine->budget_retries});   // a count, not a time
     s->timing.push_back(pm::PhaseTime{"rest_samples", (float)s->engine->last_rest});      // samples SeedExtend handed to SeedRest
+    if (s->engine->last_dense_regions) {      // the call took the suffix-array path (dense_kernels.h): how many regions, its rounds, the pass that ran out before it
+        s->timing.push_back(pm::PhaseTime{"dense_regions", (float)s->engine->last_dense_regions});
+        s->timing.push_back(pm::PhaseTime{"dense_rounds", (float)s->engine->dense_rounds});
+        if (s->engine->last_dense_overrun_ms >= 0) s->timing.push_back(pm::PhaseTime{"dense_overrun", s->engine->last_dense_overrun_ms});
+    }
     if (s->engine->last_alg[0] > 0) {      // a search of store regions: its algorithmic bytes (counts as well; the caller never held the rows)
         s->timing.push_back(pm::PhaseTime{"alg_survey", (float)s->engine->last_alg[0]});
         s->timing.push_back(pm::PhaseTime{"alg_kernel", (float)s->engine->last_alg[1]});

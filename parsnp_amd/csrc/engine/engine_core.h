@@ -18,6 +18,7 @@
 
 #include "kernels.h"
 #include "store_kernels.h"
+#include "dense_kernels.h"
 
 namespace pm {
 
@@ -169,9 +170,12 @@ public:
     // assembled in ONE page-locked block and sent by asynchronous copies on the engine's stream.
     std::vector<int64_t> mumi_covered;   // result of run(..., mumi = true): per query genome
     // A batch whose repeat structure exhausts the per-thread work budget (a tandem repeat of period > 1 with thousands of
-    // copies inside ONE region: every copy's K-mer chain is walked by every sample that hits it) is run again with a
-    // budget 256 times larger -- slow, but the reference aligns such input too; only then PM_ELIMIT.  In a sharded run the
-    // verdict is common to all ranks (it travels with the first exchange), so every rank repeats the batch together.
+    // copies inside ONE region: every copy's K-mer chain is walked by every sample that hits it) is run again.  The walk that
+    // ran out flagged its region (dense[]); in the second run the flagged regions take the suffix-array path
+    // (dense_kernels.h: rep' and the queued samples' events, at a cost independent of the copy number), every other region
+    // walks as before.  In a sharded run the verdict is common to all ranks (it travels with the first exchange), so every
+    // rank repeats the batch together, each with its own flags (the suffix array gives what a walk gives wherever one ends).
+    // A walk that runs out in the second run still fails the call (PM_ELIMIT); it cannot: the flagged regions do not walk.
     // Requests whose rows are regions of the session's region store (resident route): the host holds their reference columns only.
     struct GapBatch {
         const int64_t* ref_start = nullptr; const int64_t* ref_len = nullptr;   // [nreg]: the reference column of every region (sizes the index)
@@ -180,16 +184,29 @@ public:
     int run(int64_t nreg, const int64_t* starts, const int64_t* lens, const int32_t* minsize, BatchResult* out, bool want_events = false,
             bool mumi = false, const GapBatch* gb = nullptr) {
         budget_exceeded = false;
+        dense_mode = false; dense_h.clear(); last_dense_regions = 0; last_dense_overrun_ms = -1;      // (nothing of the path outlives a call)
+        const int64_t ordinal = call_ordinal;
+        if (dense_all && nreg > 0) { dense_h.assign((size_t)nreg, 1); dense_mode = true; }
+        const auto t0 = std::chrono::steady_clock::now();
         int rc = run_once(nreg, starts, lens, minsize, out, want_events, mumi, gb);
-        if (rc == -5 && budget_exceeded && work_budget < ((int64_t)1 << 40)) {
-            const int64_t keep = work_budget;
-            work_budget = keep << 8;
+        if (rc == -5 && budget_exceeded && !dense_mode) {
             budget_retries++;
+            last_dense_overrun_ms = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            // the flags of the pass that ran out: one download of nreg bytes, on this path only
+            dense_h.resize((size_t)nreg);
+            be.d2h(dense_h.data(), d_dense.p, (size_t)nreg);
+            (void)be.collect();          // (that pass's phases are not the second run's)
+            call_ordinal = ordinal;      // (the same call of the step: the same capacities)
+            dense_mode = true; budget_exceeded = false;
             rc = run_once(nreg, starts, lens, minsize, out, want_events, mumi, gb);
-            work_budget = keep;
         }
+        dense_mode = false;
         return rc;
     }
+    bool dense_all = false;             // pm_session_tune "dense_all": every region of every batch takes the suffix-array path (tests)
+    int64_t last_dense_regions = 0;     // regions of the last call that took the suffix-array path
+    float last_dense_overrun_ms = -1;   // ... and the time of the pass that ran out of budget before it (-1: none)
+    int dense_rounds = 0;               // prefix-doubling rounds of the last suffix-array build
     int64_t anchor_table_id = 0, anchor_table_rows = 0;      // the anchor table: rows of the last long one-region call in row mode = rows [0, A) of the MUM store
     bool budget_exceeded = false;
     long budget_retries = 0;
@@ -341,12 +358,21 @@ public:
         ensure(d_coarse, (size_t)std::max<int64_t>(centries, 1));
         ensure(d_wmask, (size_t)nwv + 1); ensure(d_wcount, (size_t)nwv + 1); ensure(d_woff, (size_t)nwv + 1);
         if (from_store_) ensure(d_alg, 8 * (size_t)kAlgSets);
+        ensure(d_dense, regz);
         {
+            // (the regions' dense flags as well -- but in the suffix-array run, which sets them from the host below)
             const ClearJob jobs[] = {
                 {d_filter.p, sizeof(uint32_t) * (size_t)fwords, 0}, {d_slots.p, sizeof(uint64_t) * (size_t)tsize, 0xff}, {d_counter.p, 8 * ncounter, 0},
                 {d_repeated.p, 4 * (size_t)(npos / 32 + 2), 0}, {d_coarse.p, 4 * (size_t)std::max<int64_t>(centries, 1), 0},
-                {d_ucount.p + npairs, 8, 0}, {d_wcount.p + nwv, 8, 0}, {from_store_ ? d_alg.p : nullptr, from_store_ ? (size_t)64 * kAlgSets : 0, 0}};
+                {d_ucount.p + npairs, 8, 0}, {d_wcount.p + nwv, 8, 0}, {from_store_ ? d_alg.p : nullptr, from_store_ ? (size_t)64 * kAlgSets : 0, 0},
+                {dense_mode ? nullptr : d_dense.p, dense_mode ? 0 : regz, 0}};
             be.clear_many(jobs, (int)(sizeof jobs / sizeof jobs[0]));
+        }
+        int64_t nflag = 0;      // the suffix-array run: regions flagged (by the pass that ran out of budget, or all: dense_all)
+        if (dense_mode) {
+            for (int64_t r = 0; r < nreg; r++) nflag += dense_h[(size_t)r] ? 1 : 0;
+            be.h2d(d_dense.p, dense_h.data(), regz);
+            last_dense_regions = nflag;
         }
         // rows the device derived itself (gaps of the anchor table, rows of the region store) were never seen by the host: the
         // same checks the explicit rows get above, raised through the batch's error word
@@ -360,7 +386,11 @@ public:
         be.mark("repeat");
         ensure(d_run, (size_t)std::max<int64_t>(npos, 1));
         be.launch("run_length", npos, RunLength{P, d_R.p, nreg, d_posbase.p, d_run.p});
-        be.launch("repeat_length", npos, RepeatLength{P, d_R.p, nreg, d_posbase.p, d_slots.p, d_filter.p, d_next.p, d_run.p, d_rep.p, d_repeated.p, d_err, work_budget});
+        be.launch("repeat_length", npos, RepeatLength{P, d_R.p, nreg, d_posbase.p, d_slots.p, d_filter.p, d_next.p, d_run.p, d_rep.p, d_repeated.p, d_err, work_budget, d_dense.p});
+        if (nflag > 0) {
+            be.mark("dense_sa");
+            if (int rc = dense_build(R, nreg, nflag)) return rc;
+        }
 
         // -- work units (pairs that fit 128 bases on both sides go to SmallPairEvents instead)
         be.mark("units");
@@ -426,7 +456,14 @@ public:
             if (nunits > 0)      // one lane per queued sample; lanes past a sub-queue's count leave at once (the counts stay on the device)
                 be.launch("seed_rest", (int64_t)(queue_cap * kSlices),
                           SeedRest{P, d_R.p, d_units.p, d_rest.p, d_qcount.p, (uint64_t)queue_cap, d_slots.p, d_filter.p, d_next.p, d_rep.p,
-                                   d_evkey.p, d_evval.p, d_counter.p, (uint64_t)slice_cap, lbits, d_err, work_budget});
+                                   d_evkey.p, d_evval.p, d_counter.p, (uint64_t)slice_cap, lbits, d_err, work_budget, d_dense.p});
+            if (nunits > 0 && nflag > 0) {      // the probe items of the flagged regions
+                be.mark("dense_search");
+                be.launch("seed_dense", (int64_t)(queue_cap * kSlices),
+                          SeedDense{P, d_R.p, d_units.p, d_rest.p, d_qcount.p, (uint64_t)queue_cap, d_dfi.p, d_dstart.p, d_dval2.p, d_rep.p,
+                                    d_evkey.p, d_evval.p, d_counter.p, (uint64_t)slice_cap, lbits});
+                be.mark("seed_extend");
+            }
             if (!no_small)
                 be.launch("small_pair_events", npairs * 2,
                           SmallPairEvents{P, d_R.p, d_starts.p, d_lens.p, ngen, d_rep.p, d_evkey.p, d_evval.p, d_counter.p, (uint64_t)slice_cap, lbits, g_first, g_last, grouping ? d_gflag.p : nullptr});
@@ -1386,6 +1423,54 @@ public:
         return 0;
     }
     std::vector<int64_t> lay_off_h;
+
+    // The suffix array of the flagged regions of a batch (dense_kernels.h) and their rep' (after RepeatLength, which skipped them).
+    // One segmented prefix-doubling sort over all of them; every round waits for its count of distinct ranks (8 bytes) -- a round
+    // trip per round, on this path only.
+    int dense_build(const RegionInfo* R, int64_t nreg, int64_t nflag) {
+        std::vector<int32_t> fi_h((size_t)nreg, -1), list_h;
+        std::vector<int64_t> start_h(1, 0);
+        for (int64_t r = 0; r < nreg; r++)
+            if (dense_h[(size_t)r]) { fi_h[(size_t)r] = (int32_t)list_h.size(); list_h.push_back((int32_t)r); start_h.push_back(start_h.back() + R[r].nR); }
+        const int64_t n = start_h.back();
+        ensure(d_dfi, (size_t)nreg); ensure(d_dlist, (size_t)nflag); ensure(d_dstart, (size_t)nflag + 1);
+        be.h2d(d_dfi.p, fi_h.data(), 4 * (size_t)nreg);
+        be.h2d(d_dlist.p, list_h.data(), 4 * (size_t)nflag);
+        be.h2d(d_dstart.p, start_h.data(), 8 * ((size_t)nflag + 1));
+        ensure(d_dval2, (size_t)std::max<int64_t>(n, 1));
+        dense_rounds = 0;
+        if (n == 0) return 0;
+        if (n >= (1ll << 31) || (uint64_t)nflag * 5 >= ((uint64_t)1 << 32)) { error = "suffix-array batch too large"; return -5; }
+        ensure(d_dkey, (size_t)n); ensure(d_dval, (size_t)n); ensure(d_dkey2, (size_t)n);
+        ensure(d_dhead, (size_t)n + 1); ensure(d_dfirst, (size_t)n + 1); ensure(d_dlcp, (size_t)n);
+        DenseLevels L{};
+        ensure(d_drank[0], (size_t)n);
+        be.launch("dense_rank0", n, DenseRank0{P, d_R.p, d_dlist.p, d_dstart.p, nflag, d_drank[0].p});
+        L.lv[0] = d_drank[0].p;
+        int64_t groups = 0;
+        int k = 0;
+        for (; k + 1 < kDenseMaxLevels; k++) {
+            // (ranks of round 0 are < 5 nflag, of later rounds < n: the sort looks at the bits they can have)
+            const uint64_t top_rank = k == 0 ? (uint64_t)nflag * 5 : (uint64_t)n;
+            be.launch("dense_keys", n, DenseKeys{d_dstart.p, nflag, d_drank[k].p, (int64_t)1 << k, d_dkey.p, d_dval.p});
+            be.sort_pairs(d_dkey.p, d_dkey2.p, d_dval.p, d_dval2.p, (size_t)n, 32 + bits_for(top_rank));
+            be.launch("dense_heads", n + 1, DenseHeads{d_dkey2.p, n, d_dhead.p});
+            be.exclusive_scan(d_dhead.p, d_dfirst.p, (size_t)n + 1);
+            ensure(d_drank[k + 1], (size_t)n);
+            be.launch("dense_rerank", n, DenseRerank{d_dval2.p, d_dhead.p, d_dfirst.p, d_drank[k + 1].p});
+            L.lv[k + 1] = d_drank[k + 1].p;
+            be.d2h(&groups, d_dfirst.p + n, 8);
+            if (groups == n) break;
+        }
+        if (groups != n) { error = "suffix-array sort did not converge"; return -5; }
+        dense_rounds = k + 1;
+        L.top = k;      // round k + 1 ranks every suffix apart: the lifting starts below it
+        be.launch("dense_lcp", n, DenseLcp{L, d_dval2.p, d_dstart.p, nflag, d_dlcp.p});
+        be.launch("dense_rep", n, DenseRep{d_R.p, d_dlist.p, d_dval2.p, d_dstart.p, nflag, d_dlcp.p, d_rep.p});
+        return 0;
+    }
+    bool dense_mode = false;            // this run of the batch takes the suffix-array path for the regions flagged in dense_h
+    std::vector<uint8_t> dense_h;
     void collect_timing_more() { for (const PhaseTime& t : be.collect()) timing.push_back(t); }
 
     // small host-side all-gather (calcmumi's per-genome results): through device staging when the collectives are RCCL
@@ -1402,7 +1487,8 @@ public:
     std::vector<uint64_t> ev_key_h, ev_val_h;
     std::vector<int32_t> rep_h;
     int ev_lbits = 0;
-    // tunables of a session (pm_session_tune): per-thread work budget of the index walks; shortest one-region candidate list
+    // tunables of a session (pm_session_tune): per-thread work budget of the index walks (a region whose walks exceed it takes the
+    // suffix-array path); shortest one-region candidate list
     // that gets the device overlap test and stays resident as the anchor table (the host's threshold for its long-list routes)
     int64_t work_budget = 1 << 22;
     int64_t dirty_min = 4096;
@@ -1444,6 +1530,7 @@ public:
         if (key == "timing") { phase_timing = value != 0; be.timing_on = phase_timing; return true; }
         if (key == "group_small") { group_small = value != 0; return true; }
         if (key == "work_budget" && value > 0) { work_budget = value; return true; }
+        if (key == "dense_all") { dense_all = value != 0; return true; }
         if (key == "dirty_min" && value >= 0) { dirty_min = value; return true; }
         return false;
     }
@@ -1515,6 +1602,10 @@ private:
     Buf<uint32_t> d_cflags, d_dirty; Buf<int32_t> d_bmax, d_bmin;
     Buf<GenomeAtK> d_xsend, d_xrecv; Buf<uint8_t> d_hsend, d_hrecv;
     Buf<RestItem> d_rest; Buf<uint64_t> d_qcount;
+    // the suffix-array path (dense_kernels.h): flags per region, flagged index per region, the flagged regions and their dense
+    // bases, sort keys / values (d_dval2: the suffix array), heads and ranks of a round, every round's ranks, LCP of SA neighbours
+    Buf<uint8_t> d_dense; Buf<int32_t> d_dfi, d_dlist, d_dlcp; Buf<int64_t> d_dstart, d_dhead, d_dfirst;
+    Buf<uint64_t> d_dkey, d_dkey2, d_dval, d_dval2; Buf<uint32_t> d_drank[kDenseMaxLevels];
     Buf<int32_t> d_anchor_start, d_anchor_lon; Buf<uint32_t> d_anchor_flags;      // the MUM store's rows as the searches delivered them
     int64_t table_counter = 0;
     Buf<uint64_t> d_image;

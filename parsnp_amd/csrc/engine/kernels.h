@@ -532,6 +532,7 @@ struct RunLength {
 struct RepeatLength {
     Packed P; const RegionInfo* R; int64_t nregions; const int64_t* posbase;
     const uint64_t* slots; const uint32_t* filter; const int32_t* next; const int32_t* run; int32_t* rep; uint32_t* repeated; uint32_t* err; int64_t budget;
+    uint8_t* dense;      // [region]: set when a walk of the region runs out of budget; a flagged region's rep' comes from its suffix array (dense_kernels.h)
     // repeated: one bit per flat reference position, set when the canonical K-mer starting there occurs elsewhere in R, in
     // either orientation (its index chain has more than one entry); n/8 bytes, L2 resident -- SeedExtend's followers read
     // it instead of probing the index
@@ -545,8 +546,8 @@ struct RepeatLength {
         if (l + ri.K <= ri.nR && h >= 0) {
             int64_t base = P.goff[0] + ri.ref_pos;
             const uint64_t slot = slots[ri.tbase + h];
-            if (slot & kMulti) {
-                shared = true;
+            if (slot & kMulti) shared = true;
+            if (shared && !dense[r]) {
                 int64_t work = 0;
                 const int32_t r1 = run[tid];
                 const bool single = r1 >= ri.K;          // the K-mer is one symbol K times: its chain holds the runs of that symbol and of its complement
@@ -569,7 +570,7 @@ struct RepeatLength {
                     }
                     if (len > best) best = len;
                     work += cost;
-                    if (work > budget) { atomic_or32(err, kErrWork); break; }
+                    if (work > budget) { atomic_or32(err, kErrWork); dense[r] = 1; break; }
                 }
             }
         }
@@ -1015,6 +1016,7 @@ struct SeedRest {
     Packed P; const RegionInfo* R; const UnitRec* units; const RestItem* queue; const uint64_t* queue_count; uint64_t queue_cap;
     const uint64_t* slots; const uint32_t* filter; const int32_t* next; const int32_t* rep;
     uint64_t* ev_key; uint64_t* ev_val; uint64_t* ev_counters; uint64_t slice_cap; int lbits; uint32_t* err; int64_t budget;
+    uint8_t* dense;      // [region]: flagged when a walk runs out of budget; the probe items of a flagged region are SeedDense's
     PM_HD void operator()(int64_t tid) const {
         const uint64_t sub = (uint64_t)tid / queue_cap, idx = (uint64_t)tid % queue_cap;
         const uint64_t have = queue_count[sub * kSliceStride];
@@ -1075,7 +1077,7 @@ struct SeedRest {
             const bool multi = (slot & kMulti) != 0;
             const int32_t head = slot_head(slot);
             for (int32_t l = head; l >= 0; l = multi ? next[ri.posbase + l] : -1) {
-                if (++work > budget) { atomic_or32(err, kErrWork); return; }
+                if (++work > budget) { atomic_or32(err, kErrWork); dense[rec.region] = 1; return; }
                 if (l == skip) continue;                    // (already handled from the registers)
                 const uint64_t rt = l == head ? head_rt : kmer_tag(P, rbase + l, K);      // (the head's K-mer was read to confirm the slot)
                 if (rt == tag) forward_seed(j, l);
@@ -1099,7 +1101,7 @@ struct SeedRest {
         if (live) {
             const int64_t j = (int64_t)it.sample * stride;
             if (it.l >= 0) reverse_seed(j, it.l);
-            else {
+            else if (!dense[rec.region]) {
                 const uint64_t tg = kmer_tag(P, qbase + j, K);
                 probe_sample(j, tg, rc_tag(tg, K));
             }

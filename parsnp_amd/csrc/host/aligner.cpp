@@ -351,7 +351,8 @@ void Aligner::collect_engine_timing() {
         for (int i = 0; i < cnt; i++) {
             if (!strcmp(names[i], "call_wall")) wall = ms[i];
             else if (strncmp(names[i], "alg_", 4) && strncmp(names[i], "n_", 2) && strcmp(names[i], "events") && strcmp(names[i], "rest_samples") && strcmp(names[i], "budget_retries") &&
-                     strcmp(names[i], "exact_cluster_tests") && strcmp(names[i], "deferred_regions") && strcmp(names[i], "tail_repeats") && strcmp(names[i], "outside_writes")) dev += ms[i];
+                     strcmp(names[i], "exact_cluster_tests") && strcmp(names[i], "deferred_regions") && strcmp(names[i], "tail_repeats") && strcmp(names[i], "outside_writes") &&
+                     strcmp(names[i], "dense_regions") && strcmp(names[i], "dense_rounds") && strcmp(names[i], "dense_overrun")) dev += ms[i];
         }
         fprintf(stderr, "[engine call] wall %.3f ms, device phases %.3f ms\n", wall, dev);
     }

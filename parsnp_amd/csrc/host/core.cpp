@@ -112,6 +112,7 @@ int CoreRun::open(const std::string& ini_path) {
     // (test builds: the engine's thresholds of the long-list routes, lowered so that small inputs take them)
     if (const char* v = test_hook("PM_DIRTY_MIN")) (void)pm_session_tune(session, "dirty_min", atol(v));
     if (const char* v = test_hook("PM_WORK_BUDGET")) (void)pm_session_tune(session, "work_budget", atol(v));
+    if (const char* v = test_hook("PM_DENSE_ALL")) (void)pm_session_tune(session, "dense_all", atol(v));
     if (const char* v = test_hook("PM_FLAGGED_DIV")) (void)pm_session_tune(session, "flagged_div", atol(v));
     if (const char* v = test_hook("PM_TANGLED_MAX")) (void)pm_session_tune(session, "tangled_max", atol(v));
     if (const char* v = test_hook("PM_ATOMIC_MARKS")) (void)pm_session_tune(session, "atomic_marks", atol(v));
