@@ -335,6 +335,30 @@ int pm_gap_align_groups(int device, int64_t n_jobs, const int32_t* n_seqs, const
                         const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols,
                         int n_groups, const int64_t* group_end, void (*done)(void* ctx, int group), void* ctx);
 const char* pm_gap_last_error(void);
+/* The same call with the device's wide form beside the narrow one.  pm_gap_align_batch and pm_gap_align_groups keep the narrow
+ * limits above exactly (512 sequences, 96 bases, 96 columns); this entry point takes every job within pm_gap_limits(1, ...):
+ * up to 512 sequences of up to 320 bases each whose intermediate alignments stay within 640 columns -- every gap that the
+ * reference driver's default --max-cluster-d 300 can produce.  A job whose sequences all have at most 96 bases runs in the narrow
+ * form (same kernel, same LDS, same workgroups per CU as in the two calls above); when the narrow form declines it and
+ * max_cols[j] > 96, it runs again in the wide form before its group is reported.  A job with a longer sequence runs in the wide
+ * form; per group the narrow jobs are launched first, then the wide ones, each longest first.
+ *   cols[j] = -1   only: fewer than 2 or more than 512 sequences, a sequence that is empty or longer than 320 bases, an
+ *                  intermediate alignment wider than 640 columns or than max_cols[j], a lower-case letter or a 'U', or a case in
+ *                  which MUSCLE itself quits.  No job is declined for the LDS it would need: rows and trace-back bytes that do not
+ *                  fit lie in the device workspace.
+ * stats (may be NULL): what the call did. */
+typedef struct pm_gap_stats {
+    int64_t jobs_narrow, jobs_wide;   /* jobs aligned by each form (a job run again in the wide form counts as wide) */
+    int64_t declined;                 /* jobs answered with cols = -1 */
+    double ms_narrow, ms_wide;        /* kernel time of each form, summed over the launches (HIP events) */
+} pm_gap_stats;
+int pm_gap_align_groups_wide(int device, int64_t n_jobs, const int32_t* n_seqs, const int64_t* seq_off, const uint8_t* chars,
+                             const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols,
+                             int n_groups, const int64_t* group_end, void (*done)(void* ctx, int group), void* ctx, pm_gap_stats* stats);
+/* The device gap aligner's limits: wide = 0 those of pm_gap_align_batch / pm_gap_align_groups, wide != 0 those of
+ * pm_gap_align_groups_wide.  max_seqs: sequences of a job; max_seq_len: bases of a sequence; max_cols: columns of an
+ * alignment.  Any pointer may be NULL.  Needs no device. */
+int pm_gap_limits(int wide, int* max_seqs, int* max_seq_len, int* max_cols);
 
 /* Device-side timing of the last pm_multi_mum_batch on this session (HIP events on the engine's stream):
  * names[i] / ms[i] for i < *count (count in: capacity, out: filled).  Used by bench.py's roofline line.

@@ -40,6 +40,15 @@ class Lib:
     def provider(self):
         return self.L.pm_provider().decode()
 
+    def gap_limits(self, wide=True):
+        """(sequences, bases of a sequence, columns of an alignment) the device gap aligner takes: pm_gap_limits -- wide: those of
+        pm_gap_align_groups_wide, else those of pm_gap_align_batch / pm_gap_align_groups"""
+        if not hasattr(self.L, "pm_gap_limits"):
+            raise PmError("this provider of the ABI has no pm_gap_limits")
+        a, b, c = C.c_int(), C.c_int(), C.c_int()
+        self._check(self.L.pm_gap_limits(C.c_int(1 if wide else 0), C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
     def _check(self, rc):
         if rc != 0:
             raise PmError("%s (code %d)" % (self.L.pm_last_error().decode(), rc))

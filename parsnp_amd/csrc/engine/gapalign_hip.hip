@@ -1,4 +1,5 @@
-// gapalign_hip.hip -- the inter-MUM gap aligner on the MI355X: pm_gap_align_batch (include/parsnp_mum.h).
+// gapalign_hip.hip -- the inter-MUM gap aligner on the MI355X: pm_gap_align_batch, pm_gap_align_groups and
+// pm_gap_align_groups_wide (include/parsnp_mum.h).
 //
 // Replaces, for a whole run's worth of gaps at once, what the reference's XMFA writer does gap by gap:
 // MuscleInterface::CallMuscleFast (src/MuscleInterface.cpp:37-78, called at src/parsnp.cpp:854-855), i.e. the one
@@ -22,6 +23,10 @@
 //   merge        aligngivenpath.cpp:124-366                 rows re-spelled through a column map, lanes over columns
 // A job the device declines (more than kMaxSeqs sequences, an alignment wider than its row capacity or kMaxCols, an
 // empty sequence, MUSCLE's own "quit" conditions) is reported with cols = -1 and stays with the caller's host path.
+// Two forms of the one kernel, a template over the limits (SharedT): the narrow form (kMaxCols = 96 bases and columns; rows and
+// trace-back bytes in LDS) and the wide form (kWideSeq = 320 bases, kWideCols = 640 columns: every gap of the reference's default
+// d = 300; rows in LDS when they fit, else -- like its trace-back bytes -- in the slot's workspace).  The first two entry points run
+// the narrow form alone, with the limits they have always had; the third splits its jobs by form (align_groups).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -31,6 +36,7 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../../include/parsnp_mum.h"
@@ -38,7 +44,9 @@
 namespace {
 
 constexpr int kMaxSeqs = 512;      // sequences per alignment on the device
-constexpr int kMaxCols = 96;       // columns of any intermediate alignment on the device (LDS per wavefront ~25 KB: 6 alignments in flight per CU)
+constexpr int kMaxCols = 96;       // narrow form: bases of a sequence and columns of any intermediate alignment (LDS per wavefront ~25 KB: 6 alignments in flight per CU)
+constexpr int kWideSeq = 320;      // wide form: bases of a sequence (every gap the default d = 300 of the reference's driver can produce) ...
+constexpr int kWideCols = 640;     // ... and columns of any intermediate alignment (300-base strings align to about 1.65 times their length)
 constexpr int kTable = 46656;      // 6^6 (fastdistnuc.cpp:82)
 constexpr float kMinusInf = (float)-1e37;
 constexpr float kBigDist = (float)1e29;
@@ -81,11 +89,14 @@ struct Slot {
     int32_t* perm;          // [n] row -> sequence
     float* total;           // [2n] sequential float sum of the weights of a node's rows, in row order
     uint8_t* table;         // [46656] 6-mer counts of one string (fastdistnuc.cpp:82), all zero between uses
+    uint8_t* rows;          // wide form, when they do not fit the LDS: the alignment rows (nmax x cap) ...
+    uint8_t* tb;            // ... and the trace-back bytes of one pairwise DP (tb_bytes)
 };
 
 struct Params {
     const Job* jobs; int64_t njobs; const int64_t* seq_off; const uint8_t* chars;
     uint8_t* out_rows; int32_t* out_cols; unsigned long long* next; uint8_t* ws; int64_t ws_stride; int32_t nmax, cap;
+    int32_t rows_ws, tb_ws;    // wide form: the rows / the trace-back bytes live in the slot's workspace, not in LDS
     volatile int32_t* dbg;     // PM_GAP_DEBUG: per slot (job, stage) in host memory the host can read while the kernel runs
     unsigned long long* prof;  // PM_GAP_DEBUG=3: shader clocks per stage, summed over the jobs
 };
@@ -127,35 +138,45 @@ __device__ inline void wave_argmin(float& v, unsigned& i) {
 // LDS of the one wavefront of a workgroup, used phase after phase (the alignment rows themselves -- n rows of `cap`
 // bytes, row p = leaf p in the order of the root alignment -- follow it as dynamic LDS: every profile is a sequential
 // sum over its rows, 20 000 row visits for 201 sequences, and from global memory each visit is a round trip)
-struct __align__(16) Shared {
+// kCols_: columns of an alignment, kSeq_: bases of a sequence -- (kMaxCols, kMaxCols) is the narrow form, (kWideCols, kWideSeq) the wide one
+template <int kCols_, int kSeq_>
+struct __align__(16) SharedT {
+    static constexpr int kCols = kCols_, kSeq = kSeq_;
+    using col_t = typename std::conditional<(kCols_ > 255), uint16_t, uint8_t>::type;      // a column count / a sequence length
   union {           // the guide tree is finished (and synchronised on) before the first profile is built
     struct { float mind[kMaxSeqs]; unsigned nearest[kMaxSeqs]; unsigned node[kMaxSeqs]; float height[kMaxSeqs]; } t;      // tree
     struct {
-            float fa[4][kMaxCols]; uint8_t orda[kMaxCols]; float opena[kMaxCols], closea[kMaxCols];   // profile A: sorted counts, their letters
-            float sb[4][kMaxCols]; float openb[kMaxCols], closeb[kMaxCols];                           // profile B: scores per letter
-            float bD[kMaxCols + 2], bM[kMaxCols + 2], bN[kMaxCols + 2]; uint8_t bX[kMaxCols + 2];     // row handed from one 64-row stripe to the next
-            uint8_t path[2 * kMaxCols + 2], rev[2 * kMaxCols + 2];
-            int16_t mapa[2 * kMaxCols + 2], mapb[2 * kMaxCols + 2];
+            float fa[4][kCols]; uint8_t orda[kCols]; float opena[kCols], closea[kCols];   // profile A: sorted counts, their letters
+            float sb[4][kCols]; float openb[kCols], closeb[kCols];                           // profile B: scores per letter
+            float bD[kCols + 2], bM[kCols + 2], bN[kCols + 2]; uint8_t bX[kCols + 2];     // row handed from one 64-row stripe to the next
+            uint8_t path[2 * kCols + 2], rev[2 * kCols + 2];
+            int16_t mapa[2 * kCols + 2], mapb[2 * kCols + 2];
         float result[3];
-        float acc[6][kMaxCols];      // a column's six sums (four letters, gap opened here, gap closed here) before they are gathered
+        float acc[6][kCols_ <= 128 ? kCols_ : 1];      // a column's six sums (four letters, gap opened here, gap closed here) before they are gathered
     } p;
   };
+    // the wide form keeps the six sums in the bytes of bD ... mapb: the hand-over row, the path and the maps of a pairwise step
+    // are dead while its two profiles are built, and 15 KB more would push the rows of a 200-sequence gap out of the LDS
+    static_assert(3 * 4 * (kCols_ + 2) + (kCols_ + 2) + 2 * (2 * kCols_ + 2) + 4 * (2 * kCols_ + 2) >= 6 * 4 * kCols_, "the sums fit");
+    __device__ float& acc(int kind, int c) { if constexpr (kCols_ <= 128) return p.acc[kind][c]; else return p.bD[kind * kCols_ + c]; }
     uint8_t letter[256];       // alpha.cpp:125-166 (c_letter, copied: a table in constant memory costs a trip to memory per lane)
     float total_i[kMaxSeqs];   // per internal node: sequential float sum of the weights of its rows, in row order
-    uint8_t ncols_i[kMaxSeqs]; // per internal node: columns of its alignment
-    uint8_t rowlen[kMaxSeqs];  // length of the sequence in row p
-    uint16_t codes[kMaxCols];
+    col_t ncols_i[kMaxSeqs];   // per internal node: columns of its alignment
+    col_t rowlen[kMaxSeqs];    // length of the sequence in row p
+    uint16_t codes[kSeq];
     float wrow[kMaxSeqs];      // weight of the sequence in row p (rows = leaves in the order of the root alignment)
     int32_t flag;
 };
+using Shared = SharedT<kMaxCols, kMaxCols>;
+using SharedWide = SharedT<kWideCols, kWideSeq>;
 
 // ---- profile of the alignment held by rows [lo, lo+ns) (nc columns) -> either the A arrays or the B arrays
 // R: the rows in LDS.  Each of a column's six sums runs over the rows one after the other (float: the order is part of the
 // result) and the sums do not meet, so each gets a lane of its own: one masked compare and one add per row, eight rows
 // fetched at a time.  A row that does not touch a sum adds +0, which changes nothing (the sums are never negative).
 // kWild: some sequence of the job holds a wildcard (N, ...); without one the per-row test for it is not compiled in.
-template <bool kWild>
-__device__ void build_profile(Shared& S, const uint8_t* R, int cap, int lo, int ns, int nc, float total, bool as_a) {
+template <bool kWild, class Sh>
+__device__ void build_profile(Sh& S, const uint8_t* R, int cap, int lo, int ns, int nc, float total, bool as_a) {
     const int lane = (int)__lane_id();
     // msa2.cpp:418-431 + msa.cpp:369-381: this alignment's weights, rescaled to sum 1.  `total` is the sequential float sum
     // of the weights in MSA order, kept per node: a merged alignment's rows are A's then B's, so its sum continues A's.
@@ -189,14 +210,14 @@ __device__ void build_profile(Shared& S, const uint8_t* R, int cap, int lo, int 
             for (int k = 0; k < 8; k++) fold(b[k], w[k]);
         }
         for (; s0 < ns; s0++) fold(col[(size_t)s0 * (size_t)cap], S.wrow[lo + s0]);
-        if (on) S.p.acc[kind][c] = acc;
+        if (on) S.acc(kind, c) = acc;
     }
     GA_SYNC();
     for (int c0 = 0; c0 < nc; c0 += 64) {
         const int c = c0 + lane;
         if (c < nc) {
-            float cnt[4] = {S.p.acc[0][c], S.p.acc[1][c], S.p.acc[2][c], S.p.acc[3][c]};
-            const float start = S.p.acc[4][c], end = S.p.acc[5][c];
+            float cnt[4] = {S.acc(0, c), S.acc(1, c), S.acc(2, c), S.acc(3, c)};
+            const float start = S.acc(4, c), end = S.acc(5, c);
             unsigned order[4] = {0, 1, 2, 3};       // profilefrommsa.cpp:180-204: bubble sort, strict <
             bool any = true;
             for (int pass = 0; any && pass < 8; pass++) {     // at most 3 passes move anything
@@ -226,7 +247,8 @@ __device__ void build_profile(Shared& S, const uint8_t* R, int cap, int lo, int 
 }
 
 // scorepp.cpp:83-95 with all four terms (a count of 0 ends the reference's loop; its term is +-0 here, the zeros come last)
-__device__ inline float match_ab(const Shared& S, const float f[4], uint8_t ord, int j) {
+template <class Sh>
+__device__ inline float match_ab(const Sh& S, const float f[4], uint8_t ord, int j) {
     float sc = 0.0f;
     sc += f[0] * S.p.sb[ord & 3][j];
     sc += f[1] * S.p.sb[(ord >> 2) & 3][j];
@@ -236,7 +258,8 @@ __device__ inline float match_ab(const Shared& S, const float f[4], uint8_t ord,
 }
 
 // nwsmall.cpp:447-620 + bittraceback.cpp:130-209 -> S.p.path[0..*plen) in forward order; false = the reference gives up
-__device__ bool nw_small(Shared& S, uint8_t* TB, int la, int lb, int* plen, bool prof, unsigned long long& prof_sweep, unsigned long long& prof_t0) {
+template <class Sh>
+__device__ bool nw_small(Sh& S, uint8_t* TB, int la, int lb, int* plen, bool prof, unsigned long long& prof_sweep, unsigned long long& prof_t0) {
     const int lane = (int)__lane_id();
     const float e = kGapExtend;
     const int stride = lb + 1;
@@ -244,6 +267,8 @@ __device__ bool nw_small(Shared& S, uint8_t* TB, int la, int lb, int* plen, bool
         S.p.opena[0] = 0.0f * -1.0f; if (la > 1) S.p.closea[la - 1] = 0.0f * -1.0f;
         S.p.openb[0] = 0.0f * -1.0f; if (lb > 1) S.p.closeb[lb - 1] = 0.0f * -1.0f;
     }
+    // (the trace-back bytes: a (la + 1) x (lb + 1) matrix, row 0 and column 0 zero.  In the wide form it usually lies in the slot's
+    // workspace; storing the 64 bytes of a step next to each other instead was measured and changed nothing: DESIGN.md 6-W)
     for (int x = lane; x <= la; x += 64) TB[x * stride] = 0;
     for (int x = lane; x <= lb; x += 64) TB[x] = 0;
     GA_SYNC();
@@ -332,7 +357,7 @@ __device__ bool nw_small(Shared& S, uint8_t* TB, int la, int lb, int* plen, bool
         int a = la, b = lb, n = 0;
         uint8_t* rev = S.p.rev;        // end to start, as the trace-back meets the cells
         for (;;) {                     // one dependent LDS read per cell: the rest is selects, not branches
-            if (n >= 2 * kMaxCols + 2) { ok = false; break; }
+            if (n >= 2 * Sh::kCols + 2) { ok = false; break; }
             rev[n++] = type == 0 ? (uint8_t)'M' : (type == 1 ? (uint8_t)'D' : (uint8_t)'I');
             const uint32_t bits = TB[a * stride + b];
             const uint32_t x = bits & kXM;
@@ -383,10 +408,11 @@ constexpr bool ga_stage_on(int s) { return kGapStages && !(PM_GAP_STRIP_STAGE ==
 // hung (round 3; reproduced, bisected to the two job markers of the kernel's loop and read off the ISA in round 5: DESIGN.md 9-6,
 // scripts/gap_nomark.sh).  As a call the job is one node of the loop's control flow; -DPM_GAP_INLINE restores the old shape for the
 // regression check.  tests/test_gpu_gapalign.py::test_marker_free_build runs the marker-free build.
+template <class Sh>
 #if !defined(PM_GAP_INLINE)
 __attribute__((noinline))
 #endif
-__device__ bool align_job(Shared& S, uint8_t* R, uint8_t* TB, const Slot& W, const Params& P, const Job& job, int* out_cols) {
+__device__ bool align_job(Sh& S, uint8_t* R, uint8_t* TB, const Slot& W, const Params& P, const Job& job, int* out_cols) {
     const int lane = (int)__lane_id();
     const int n = job.n, cap = P.cap;
     unsigned long long prof_acc[kProfStages] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -398,7 +424,7 @@ __device__ bool align_job(Shared& S, uint8_t* R, uint8_t* TB, const Slot& W, con
         const int64_t a = P.seq_off[job.first_seq + i], b = P.seq_off[job.first_seq + i + 1];
         const int L = (int)(b - a);
         W.len[i] = L;
-        if (L <= 0 || L > cap || L > kMaxCols) bad = 1;
+        if (L <= 0 || L > cap || L > Sh::kSeq) bad = 1;
         uint64_t h = 1469598103934665603ull;
         for (int x = 0; x < L; x++) {
             uint8_t ch = P.chars[a + x];
@@ -462,7 +488,7 @@ __device__ bool align_job(Shared& S, uint8_t* R, uint8_t* TB, const Slot& W, con
                 const unsigned long long m = __ballot(emit);
                 if (emit) {
                     const int at = nt + __popcll(m & ((1ull << lane) - 1));
-                    W.tcode[(size_t)a * kMaxCols + at] = S.codes[p]; W.tcnt[(size_t)a * kMaxCols + at] = (uint8_t)(cnt & 255);
+                    W.tcode[(size_t)a * Sh::kSeq + at] = S.codes[p]; W.tcnt[(size_t)a * Sh::kSeq + at] = (uint8_t)(cnt & 255);
                 }
                 nt += __popcll(m);
             }
@@ -473,20 +499,20 @@ __device__ bool align_job(Shared& S, uint8_t* R, uint8_t* TB, const Slot& W, con
     GA_SYNC();
     for (int a = 0; a < u; a++) {
         const int na = uni(W.ntup[a]);
-        for (int t = lane; t < na; t += 64) W.table[W.tcode[(size_t)a * kMaxCols + t]] = W.tcnt[(size_t)a * kMaxCols + t];
+        for (int t = lane; t < na; t += 64) W.table[W.tcode[(size_t)a * Sh::kSeq + t]] = W.tcnt[(size_t)a * Sh::kSeq + t];
         GA_SYNC();
         for (int b = 0; b <= a; b++) {
             const int nb = uni(W.ntup[b]);
             int sum = 0;
             for (int t = lane; t < nb; t += 64) {
-                const uint8_t c1 = W.table[W.tcode[(size_t)b * kMaxCols + t]], c2 = W.tcnt[(size_t)b * kMaxCols + t];
+                const uint8_t c1 = W.table[W.tcode[(size_t)b * Sh::kSeq + t]], c2 = W.tcnt[(size_t)b * Sh::kSeq + t];
                 sum += c1 < c2 ? c1 : c2;
             }
             sum = wave_sum(sum);
             if (lane == 0) { W.ucommon[(size_t)a * u + b] = (uint16_t)sum; W.ucommon[(size_t)b * u + a] = (uint16_t)sum; }
         }
         GA_SYNC();
-        for (int t = lane; t < na; t += 64) W.table[W.tcode[(size_t)a * kMaxCols + t]] = 0;
+        for (int t = lane; t < na; t += 64) W.table[W.tcode[(size_t)a * Sh::kSeq + t]] = 0;
         GA_SYNC();
     }
     GA_STAGE(3); GA_CLOCK(2);
@@ -609,7 +635,7 @@ __device__ bool align_job(Shared& S, uint8_t* R, uint8_t* TB, const Slot& W, con
         const int64_t a0 = P.seq_off[job.first_seq + i];
         for (int x = 0; x < L; x++) { const uint8_t l = S.letter[P.chars[a0 + x]]; row[x] = l >= 16 ? (uint8_t)15 : l; }      // FixAlpha (seq.cpp:331-344): anything else is an 'N'
 
-        S.wrow[p] = W.weight[i]; S.rowlen[p] = (uint8_t)L;
+        S.wrow[p] = W.weight[i]; S.rowlen[p] = (typename Sh::col_t)L;
     }
     GA_SYNC();
     GA_STAGE(7); GA_CLOCK(7);
@@ -633,7 +659,7 @@ __device__ bool align_job(Shared& S, uint8_t* R, uint8_t* TB, const Slot& W, con
         const int lb = uni(b < un ? (int)S.rowlen[lob] : (int)S.ncols_i[b - un]);
         const float total_a = a < un ? 0.0f + S.wrow[loa] : S.total_i[a - un];
         const float total_b = b < un ? 0.0f + S.wrow[lob] : S.total_i[b - un];
-        if (la <= 0 || lb <= 0 || la > kMaxCols || lb > kMaxCols) return false;
+        if (la <= 0 || lb <= 0 || la > Sh::kCols || lb > Sh::kCols) return false;
         if (ga_stage_on(100)) GA_STAGE_DYN(100 + (int)(v - un) * 10);
         GA_CLOCK(8);
         if (any_wild) { build_profile<true>(S, R, cap, loa, nsa, la, total_a, true); build_profile<true>(S, R, cap, lob, nsb, lb, total_b, false); }
@@ -642,7 +668,7 @@ __device__ bool align_job(Shared& S, uint8_t* R, uint8_t* TB, const Slot& W, con
         if (ga_stage_on(100)) GA_STAGE_DYN(101 + (int)(v - un) * 10); GA_CLOCK(13);
         if (!nw_small(S, TB, la, lb, &plen, kGapClocks && P.prof != nullptr, prof_acc[9], prof_t0)) return false;
         if (ga_stage_on(100)) GA_STAGE_DYN(102 + (int)(v - un) * 10); GA_CLOCK(10);
-        if (plen > cap || plen > kMaxCols) return false;
+        if (plen > cap || plen > Sh::kCols) return false;
         // aligngivenpath.cpp:124-255: a column of A, of B, or of both
         // (a column's place in A / in B = the number of A / B columns before it: counted with ballots)
         {
@@ -664,7 +690,7 @@ __device__ bool align_job(Shared& S, uint8_t* R, uint8_t* TB, const Slot& W, con
         // rows re-spelled in place through the column maps.  An input with no column inserted keeps its rows as they are
         // (the map is the identity): when one sequence joins a large alignment, that is usually the large one.  Every lane
         // reads its (at most two) characters of a row before any lane writes: one wavefront, LDS operations in program order.
-        static_assert(kMaxCols <= 128, "two columns per lane");
+        if constexpr (Sh::kCols <= 128)      // two columns per lane
         {
             const int c1 = lane, c2 = lane + 64;
             const int ma1 = c1 < plen ? S.p.mapa[c1] : -1, ma2 = c2 < plen ? S.p.mapa[c2] : -1;
@@ -704,8 +730,49 @@ __device__ bool align_job(Shared& S, uint8_t* R, uint8_t* TB, const Slot& W, con
             if (plen != la) respell(loa, nsa, ma1, ma2);
             if (plen != lb) respell(lob, nsb, mb1, mb2);
         }
+        else {
+            // more than two columns per lane: the same in chunks of 64 columns.  A column's source lies at or to the left of it
+            // (the maps count columns), so the chunks go from the right end to the left: what a chunk overwrites, no later chunk
+            // reads.  The gap flags need the finished codes of both neighbours, across chunks: a second pass over the rows.
+            auto respell = [&](int p0, int np, const int16_t* map) {
+                for (int s0 = 0; s0 < np; s0 += 4) {
+                    for (int c0 = ((plen - 1) / 64) * 64; c0 >= 0; c0 -= 64) {
+                        const int c = c0 + lane;
+                        const int m = c < plen ? (int)map[c] : -1;
+                        uint8_t v[4];
+#pragma unroll
+                        for (int k = 0; k < 4; k++) {
+                            const uint8_t* row = R + (size_t)(p0 + (s0 + k < np ? s0 + k : np - 1)) * (size_t)cap;
+                            v[k] = m >= 0 ? (uint8_t)(row[m] & kRowCode) : kRowGap;
+                        }
+                        GA_SYNC();      // (the rows may live in the slot's workspace: every lane has read before any lane writes)
+#pragma unroll
+                        for (int k = 0; k < 4; k++) {
+                            if (s0 + k >= np || c >= plen) continue;
+                            R[(size_t)(p0 + s0 + k) * (size_t)cap + c] = v[k];
+                        }
+                        GA_SYNC();
+                    }
+                    for (int c0 = 0; c0 < plen; c0 += 64) {
+                        const int c = c0 + lane;
+                        if (c >= plen) continue;
+#pragma unroll
+                        for (int k = 0; k < 4; k++) {
+                            if (s0 + k >= np) continue;
+                            uint8_t* row = R + (size_t)(p0 + s0 + k) * (size_t)cap;
+                            if (!row_gap(row[c])) continue;
+                            const uint8_t l = c > 0 ? row[c - 1] : (uint8_t)0, r = c + 1 < plen ? row[c + 1] : (uint8_t)0;
+                            row[c] = (uint8_t)(kRowGap | (row_gap(l) ? 0 : kRowStart) | (row_gap(r) ? 0 : kRowEnd));
+                        }
+                    }
+                    GA_SYNC();
+                }
+            };
+            if (plen != la) respell(loa, nsa, S.p.mapa);
+            if (plen != lb) respell(lob, nsb, S.p.mapb);
+        }
         if (lane == 0) {
-            S.ncols_i[v - un] = (uint8_t)plen;
+            S.ncols_i[v - un] = (typename Sh::col_t)plen;
             float t = total_a;                       // the merged alignment's rows: A's, then B's
             for (int x = 0; x < nsb; x++) t += S.wrow[lob + x];
             S.total_i[v - un] = t;
@@ -727,15 +794,18 @@ __device__ bool align_job(Shared& S, uint8_t* R, uint8_t* TB, const Slot& W, con
     return true;
 }
 
-__device__ Slot carve(uint8_t* base, int nmax, int cap) {
+// the trace-back bytes of one pairwise DP of up to cap x cap columns (nw_small)
+__host__ __device__ inline size_t tb_bytes(int cap) { return ((size_t)cap + 1) * ((size_t)cap + 1); }
+// seq: the form's limit on the bases of a sequence; rows / tb: the alignment rows and the trace-back bytes are in the workspace
+__device__ Slot carve(uint8_t* base, int nmax, int cap, int seq, bool rows, bool tb) {
     Slot W;
     size_t off = 0;
     auto take = [&](size_t bytes) { uint8_t* p = base + off; off += (bytes + 15) & ~(size_t)15; return p; };
     const size_t n = (size_t)nmax;
     W.dist = (float*)take(4 * (n * (n - 1) / 2 + 1));
     W.ucommon = (uint16_t*)take(2 * n * n);
-    W.tcode = (uint16_t*)take(2 * n * kMaxCols);
-    W.tcnt = take(n * kMaxCols);
+    W.tcode = (uint16_t*)take(2 * n * (size_t)seq);
+    W.tcnt = take(n * (size_t)seq);
     W.ntup = (int32_t*)take(4 * n);
     W.hash = (uint64_t*)take(8 * n);
     W.len = (int32_t*)take(4 * n); W.cls = (int32_t*)take(4 * n); W.repidx = (int32_t*)take(4 * n); W.replist = (int32_t*)take(4 * n);
@@ -749,21 +819,38 @@ __device__ Slot carve(uint8_t* base, int nmax, int cap) {
     W.perm = (int32_t*)take(4 * n);
     W.total = (float*)take(8 * n);
     W.table = take(kTable);
+    W.rows = rows ? take(n * (size_t)cap) : nullptr;
+    W.tb = tb ? take(tb_bytes(cap)) : nullptr;
     return W;
 }
-size_t slot_bytes(int nmax, int cap) {
+size_t slot_bytes(int nmax, int cap, int seq, bool rows, bool tb) {
     const size_t n = (size_t)nmax;
     auto r = [](size_t b) { return (b + 15) & ~(size_t)15; };
-    return r(4 * (n * (n - 1) / 2 + 1)) + r(2 * n * n) + r(2 * n * kMaxCols) + r(n * kMaxCols) + r(4 * n) + r(8 * n) + 4 * r(4 * n) + 3 * r(8 * n) + r(16 * n) +
-           r(4 * n) + r(8 * n) + r(16 * n) + r(4 * n) + 2 * r(8 * n) + r(4 * n) + r(8 * n) + r(kTable) + 256;
+    return r(4 * (n * (n - 1) / 2 + 1)) + r(2 * n * n) + r(2 * n * (size_t)seq) + r(n * (size_t)seq) + r(4 * n) + r(8 * n) + 4 * r(4 * n) + 3 * r(8 * n) + r(16 * n) +
+           r(4 * n) + r(8 * n) + r(16 * n) + r(4 * n) + 2 * r(8 * n) + r(4 * n) + r(8 * n) + r(kTable) + (rows ? r(n * (size_t)cap) : 0) +
+           (tb ? r(tb_bytes(cap)) : 0) + 256;
 }
 
+// Sh = Shared: the narrow form, its fixed block static and rows + trace-back bytes behind it as dynamic LDS.
+// Sh = SharedWide: the fixed block itself is dynamic LDS (54 KB), then the rows and the trace-back bytes -- each only when the launch
+// found room for it (Params::rows_ws / tb_ws: it is in the slot's workspace instead; align_job reads both through flat pointers)
+template <class Sh>
 __global__ __launch_bounds__(64) void gap_align_kernel(Params P) {
-    __shared__ Shared S;
     extern __shared__ __align__(16) uint8_t rows_lds[];      // nmax rows of cap bytes, then the (cap+1)^2 trace-back bytes of one pairwise DP
-    uint8_t* const tb_lds = rows_lds + ((((size_t)P.nmax * (size_t)P.cap) + 15) & ~(size_t)15);
+    constexpr bool kWide = Sh::kCols > kMaxCols;
+    const Slot W = carve(P.ws + (size_t)blockIdx.x * (size_t)P.ws_stride, P.nmax, P.cap, Sh::kSeq, kWide && P.rows_ws, kWide && P.tb_ws);
+    Sh* Sp; uint8_t* R; uint8_t* TB;
+    if constexpr (!kWide) {
+        __shared__ Sh S_fixed;
+        Sp = &S_fixed; R = rows_lds; TB = rows_lds + ((((size_t)P.nmax * (size_t)P.cap) + 15) & ~(size_t)15);
+    } else {
+        Sp = reinterpret_cast<Sh*>(rows_lds);
+        uint8_t* at = rows_lds + ((sizeof(Sh) + 15) & ~(size_t)15);
+        if (P.rows_ws) R = W.rows; else { R = at; at += (((size_t)P.nmax * (size_t)P.cap) + 15) & ~(size_t)15; }
+        TB = P.tb_ws ? W.tb : at;
+    }
+    Sh& S = *Sp;
     for (int x = (int)threadIdx.x; x < 256; x += 64) S.letter[x] = c_letter[x];
-    const Slot W = carve(P.ws + (size_t)blockIdx.x * (size_t)P.ws_stride, P.nmax, P.cap);
     for (int x = (int)threadIdx.x; x < kTable; x += 64) W.table[x] = 0;
     GA_SYNC();
     for (;;) {
@@ -775,7 +862,7 @@ __global__ __launch_bounds__(64) void gap_align_kernel(Params P) {
         const Job job = P.jobs[j];
         if (ga_stage_on(900) && P.dbg && threadIdx.x == 0) { P.dbg[blockIdx.x * 2] = (int32_t)j; P.dbg[blockIdx.x * 2 + 1] = 0; }
         int cols = -1;
-        if (!align_job(S, rows_lds, tb_lds, W, P, job, &cols)) cols = -1;
+        if (!align_job(S, R, TB, W, P, job, &cols)) cols = -1;
         GA_SYNC();
         if (threadIdx.x == 0) P.out_cols[j] = cols;
         if (ga_stage_on(900) && P.dbg && threadIdx.x == 0) P.dbg[blockIdx.x * 2 + 1] = -1;
@@ -838,16 +925,15 @@ extern "C" int64_t pm_gap_debug_peek(int32_t* out, int64_t cap) {
     return n;
 }
 
-extern "C" int pm_gap_align_batch(int device, int64_t n_jobs, const int32_t* n_seqs, const int64_t* seq_off, const uint8_t* chars,
-                                  const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols) {
-    return pm_gap_align_groups(device, n_jobs, n_seqs, seq_off, chars, max_cols, row_off, out_rows, out_bytes, cols, 1, &n_jobs, nullptr, nullptr);
-}
-// The same batch in groups of consecutive jobs (group g = jobs [group_end[g-1], group_end[g])): everything is uploaded once,
-// the groups are aligned one after the other, and when the rows and column counts of a group are in the caller's memory
-// `done(ctx, g)` is called (from this thread) -- the caller can start using them while the later groups are still running.
-extern "C" int pm_gap_align_groups(int device, int64_t n_jobs, const int32_t* n_seqs, const int64_t* seq_off, const uint8_t* chars,
-                                   const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols,
-                                   int n_groups, const int64_t* group_end, void (*done)(void* ctx, int group), void* ctx) {
+namespace {
+// One call of any of the three entry points.  wide = false: pm_gap_align_batch / pm_gap_align_groups, the narrow form alone, with the
+// limits and the launch they have always had.  wide = true: pm_gap_align_groups_wide -- a job with a sequence of more than kMaxCols
+// bases goes to the wide form, and a job the narrow form declined whose rows may be wider than kMaxCols is run again in the wide
+// form before its group is reported.
+int align_groups(bool wide, int device, int64_t n_jobs, const int32_t* n_seqs, const int64_t* seq_off, const uint8_t* chars,
+                 const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols,
+                 int n_groups, const int64_t* group_end, void (*done)(void* ctx, int group), void* ctx, pm_gap_stats* stats) {
+    if (stats) *stats = pm_gap_stats{0, 0, 0, 0.0, 0.0};
     if (n_jobs < 0 || (n_jobs > 0 && (!n_seqs || !seq_off || !chars || !max_cols || !row_off || !out_rows || !cols))) return fail(PM_EINVAL, "bad argument");
     if (n_groups < 1 || !group_end || group_end[n_groups - 1] != n_jobs) return fail(PM_EINVAL, "bad job groups");
     for (int g = 0; g < n_groups; g++) if (group_end[g] < (g ? group_end[g - 1] : 0)) return fail(PM_EINVAL, "bad job groups");
@@ -860,7 +946,9 @@ extern "C" int pm_gap_align_groups(int device, int64_t n_jobs, const int32_t* n_
 #define GA_CHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { release(); return fail(PM_EHIP, std::string(#x) + ": " + hipGetErrorString(e_)); } } while (0)
     std::vector<void*> owned;
     hipStream_t stream = nullptr;
-    auto release = [&]() { for (void* p : owned) (void)hipFree(p); owned.clear(); if (stream) { (void)hipStreamDestroy(stream); stream = nullptr; } };
+    std::vector<hipEvent_t> events;
+    auto release = [&]() { for (void* p : owned) (void)hipFree(p); owned.clear(); for (hipEvent_t e : events) (void)hipEventDestroy(e); events.clear();
+                           if (stream) { (void)hipStreamDestroy(stream); stream = nullptr; } };
     {
         hipError_t table_err = hipSuccess;
         int cur_dev = 0;
@@ -880,35 +968,44 @@ extern "C" int pm_gap_align_groups(int device, int64_t n_jobs, const int32_t* n_
         }
         GA_CHECK(table_err);
     }
-    // jobs the device takes, longest first (the cost of one alignment grows with the square of its width)
-    std::vector<Job> jobs; std::vector<int64_t> which; std::vector<int> group_of_job;
+    // jobs the device takes, per group the narrow ones and then the wide ones, each longest first (the cost of one alignment grows
+    // with the square of its width)
+    std::vector<Job> jobs; std::vector<int64_t> which; std::vector<int> group_of_job, form_of_job;
     int64_t seq = 0, total_chars = 0;
-    int nmax = 2, cap = 1;
+    int nmax = 2, cap = 1;             // of the narrow form: the widest job of the call
     std::vector<int> widest((size_t)n_jobs, 0);
+    const int seq_limit = wide ? kWideSeq : kMaxCols;
     int grp = 0;
     for (int64_t j = 0; j < n_jobs; j++) {
         while (grp + 1 < n_groups && j >= group_end[grp]) grp++;
         cols[j] = -1;
         const int n = n_seqs[j];
         int w = 0; bool ok = n >= 2 && n <= kMaxSeqs && max_cols[j] >= 1;
-        for (int i = 0; i < n && ok; i++) { const int64_t L = seq_off[seq + i + 1] - seq_off[seq + i]; if (L <= 0 || L > kMaxCols) ok = false; else w = std::max<int>(w, (int)L); }
+        for (int i = 0; i < n && ok; i++) { const int64_t L = seq_off[seq + i + 1] - seq_off[seq + i]; if (L <= 0 || L > seq_limit) ok = false; else w = std::max<int>(w, (int)L); }
         if (ok && row_off[j] + (int64_t)n * max_cols[j] > out_bytes) ok = false;
-        if (ok) { jobs.push_back(Job{seq, n, max_cols[j], row_off[j]}); which.push_back(j); group_of_job.push_back(grp); widest[(size_t)j] = w; nmax = std::max(nmax, n); cap = std::max(cap, std::min<int>(max_cols[j], kMaxCols)); }
+        if (ok) {
+            const int form = w > kMaxCols ? 1 : 0;
+            jobs.push_back(Job{seq, n, max_cols[j], row_off[j]}); which.push_back(j); group_of_job.push_back(grp); form_of_job.push_back(form); widest[(size_t)j] = w;
+            if (!form) { nmax = std::max(nmax, n); cap = std::max(cap, std::min<int>(max_cols[j], kMaxCols)); }
+        }
         seq += n;
     }
     total_chars = seq_off[seq];
-    if (jobs.empty()) { all_done(0); return PM_OK; }
-    std::vector<size_t> first_of_group((size_t)n_groups + 1, 0);      // in the sorted job list
+    auto count_declined = [&]() { if (stats) { stats->declined = 0; for (int64_t j = 0; j < n_jobs; j++) stats->declined += cols[j] < 0; } };
+    if (jobs.empty()) { count_declined(); all_done(0); return PM_OK; }
+    // in the sorted job list: group g = [first[2g], first[2g+2]), its narrow jobs first, its wide jobs from first[2g+1]
+    std::vector<size_t> first((size_t)n_groups * 2 + 1, 0);
     {
         std::vector<size_t> order(jobs.size());
         for (size_t i = 0; i < order.size(); i++) order[i] = i;
         std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) {
             if (group_of_job[a] != group_of_job[b]) return group_of_job[a] < group_of_job[b];
+            if (form_of_job[a] != form_of_job[b]) return form_of_job[a] < form_of_job[b];
             return widest[(size_t)which[a]] > widest[(size_t)which[b]];
         });
         std::vector<Job> j2; std::vector<int64_t> w2;
-        for (size_t i : order) { j2.push_back(jobs[i]); w2.push_back(which[i]); first_of_group[(size_t)group_of_job[i] + 1]++; }
-        for (int g = 0; g < n_groups; g++) first_of_group[(size_t)g + 1] += first_of_group[(size_t)g];
+        for (size_t i : order) { j2.push_back(jobs[i]); w2.push_back(which[i]); first[(size_t)group_of_job[i] * 2 + (size_t)form_of_job[i] + 1]++; }
+        for (size_t k = 0; k < (size_t)n_groups * 2; k++) first[k + 1] += first[k];
         jobs.swap(j2); which.swap(w2);
     }
     const bool timers = getenv("PARSNP_DEBUG_TIMERS") != nullptr;
@@ -918,68 +1015,142 @@ extern "C" int pm_gap_align_groups(int device, int64_t n_jobs, const int32_t* n_
     hipDeviceProp_t prop;
     if (device < 0) GA_CHECK(hipGetDevice(&device));      // the current device of this thread
     GA_CHECK(hipGetDeviceProperties(&prop, device));
-    // LDS of a workgroup: the fixed block plus the alignment rows of the widest job; as many workgroups per CU as fit in 160 KB
-    const size_t rows_lds = ((((size_t)nmax * (size_t)cap) + 15) & ~(size_t)15) + ((((size_t)cap + 1) * ((size_t)cap + 1) + 15) & ~(size_t)15);
-    const size_t lds = sizeof(Shared) + rows_lds;
-    if (lds > 160 * 1024 - 1024) { release(); return fail(PM_ELIMIT, "gap alignment rows do not fit the LDS"); }
-    if (lds > 64 * 1024) GA_CHECK(hipFuncSetAttribute((const void*)gap_align_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rows_lds));
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / (lds + 256)));
-    const int64_t slots = std::min<int64_t>((int64_t)jobs.size(), (int64_t)prop.multiProcessorCount * per_cu);
-    const size_t stride = slot_bytes(nmax, cap);
     GA_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     auto dalloc = [&](size_t bytes, void** p) { hipError_t e = hipMalloc(p, bytes ? bytes : 1); if (e == hipSuccess) owned.push_back(*p); return e; };
-    Job* d_jobs; int64_t* d_off; uint8_t* d_chars; uint8_t* d_out; int32_t* d_cols; unsigned long long* d_next; uint8_t* d_ws;
+    const bool any_narrow = [&] { for (int g = 0; g < n_groups; g++) if (first[(size_t)g * 2 + 1] > first[(size_t)g * 2]) return true; return false; }();
+    // ---- the narrow form.  LDS of a workgroup: the fixed block plus the alignment rows of the widest job and the trace-back bytes;
+    // as many workgroups per CU as fit in 160 KB
+    constexpr size_t kLdsLimit = 160 * 1024 - 1024;
+    const size_t rows_lds = ((((size_t)nmax * (size_t)cap) + 15) & ~(size_t)15) + ((((size_t)cap + 1) * ((size_t)cap + 1) + 15) & ~(size_t)15);
+    const size_t lds = sizeof(Shared) + rows_lds;
+    int per_cu = 0; int64_t slots = 0; size_t stride = 0;
+    uint8_t* d_ws = nullptr;
+    if (any_narrow) {
+        if (lds > kLdsLimit) { release(); return fail(PM_ELIMIT, "gap alignment rows do not fit the LDS"); }
+        if (lds > 64 * 1024) GA_CHECK(hipFuncSetAttribute((const void*)gap_align_kernel<Shared>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rows_lds));
+        per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / (lds + 256)));
+        size_t most = 0;      // narrow jobs of one group (without a wide job in the call: of the call, as the launch has always been sized)
+        for (int g = 0; g < n_groups; g++) most = std::max(most, first[(size_t)g * 2 + 1] - first[(size_t)g * 2]);
+        slots = std::min<int64_t>(wide ? (int64_t)most : (int64_t)jobs.size(), (int64_t)prop.multiProcessorCount * per_cu);
+        stride = slot_bytes(nmax, cap, kMaxCols, false, false);
+    }
+    Job* d_jobs; int64_t* d_off; uint8_t* d_chars; uint8_t* d_out; int32_t* d_cols; unsigned long long* d_next;
     GA_CHECK(dalloc(sizeof(Job) * jobs.size(), (void**)&d_jobs));
     GA_CHECK(dalloc(8 * (size_t)(seq + 1), (void**)&d_off));
     GA_CHECK(dalloc((size_t)total_chars, (void**)&d_chars));
     GA_CHECK(dalloc((size_t)out_bytes, (void**)&d_out));
     GA_CHECK(dalloc(4 * jobs.size(), (void**)&d_cols));
-    GA_CHECK(dalloc(8 * (size_t)n_groups, (void**)&d_next));
-    GA_CHECK(dalloc(stride * (size_t)slots, (void**)&d_ws));
+    GA_CHECK(dalloc(8 * 3 * (size_t)n_groups, (void**)&d_next));      // a queue counter per launch: narrow, wide, wide again
+    if (any_narrow) GA_CHECK(dalloc(stride * (size_t)slots, (void**)&d_ws));
     GA_CHECK(hipMemcpyAsync(d_jobs, jobs.data(), sizeof(Job) * jobs.size(), hipMemcpyHostToDevice, stream));
     GA_CHECK(hipMemcpyAsync(d_off, seq_off, 8 * (size_t)(seq + 1), hipMemcpyHostToDevice, stream));
     GA_CHECK(hipMemcpyAsync(d_chars, chars, (size_t)total_chars, hipMemcpyHostToDevice, stream));
-    GA_CHECK(hipMemsetAsync(d_next, 0, 8 * (size_t)n_groups, stream));
+    GA_CHECK(hipMemsetAsync(d_next, 0, 8 * 3 * (size_t)n_groups, stream));
     if (timers) { GA_CHECK(hipStreamSynchronize(stream)); lap("alloc + h2d"); }
     int32_t* dbg = nullptr;
+    const int64_t dbg_slots = std::max<int64_t>(slots, wide ? (int64_t)prop.multiProcessorCount * 8 : 0);
     if (getenv("PM_GAP_DEBUG") && atoi(getenv("PM_GAP_DEBUG")) == 2) {
         if (g_dbg_dev) (void)hipFree(g_dbg_dev);
         g_dbg_dev = nullptr;
-        if (hipMalloc((void**)&g_dbg_dev, 8 * (size_t)slots) == hipSuccess) { g_dbg_slots = slots; (void)hipMemsetAsync(g_dbg_dev, 0xff, 8 * (size_t)slots, stream); dbg = g_dbg_dev; }
+        if (hipMalloc((void**)&g_dbg_dev, 8 * (size_t)dbg_slots) == hipSuccess) { g_dbg_slots = dbg_slots; (void)hipMemsetAsync(g_dbg_dev, 0xff, 8 * (size_t)dbg_slots, stream); dbg = g_dbg_dev; }
     } else if (getenv("PM_GAP_DEBUG")) {
-        if (!g_dbg || g_dbg_slots < slots) { if (g_dbg) (void)hipHostFree(g_dbg); g_dbg = nullptr; if (hipHostMalloc((void**)&g_dbg, 8 * (size_t)slots, hipHostMallocMapped) == hipSuccess) g_dbg_slots = slots; }
-        if (g_dbg) { memset(g_dbg, 0xff, 8 * (size_t)slots); (void)hipHostGetDevicePointer((void**)&dbg, g_dbg, 0); }
+        if (!g_dbg || g_dbg_slots < dbg_slots) { if (g_dbg) (void)hipHostFree(g_dbg); g_dbg = nullptr; if (hipHostMalloc((void**)&g_dbg, 8 * (size_t)dbg_slots, hipHostMallocMapped) == hipSuccess) g_dbg_slots = dbg_slots; }
+        if (g_dbg) { memset(g_dbg, 0xff, 8 * (size_t)g_dbg_slots); (void)hipHostGetDevicePointer((void**)&dbg, g_dbg, 0); }
     }
     unsigned long long* d_prof = nullptr;
     if (getenv("PM_GAP_DEBUG") && atoi(getenv("PM_GAP_DEBUG")) == 3) {
         GA_CHECK(dalloc(8 * kProfStages, (void**)&d_prof));
         GA_CHECK(hipMemsetAsync(d_prof, 0, 8 * kProfStages, stream));
     }
-    if (timers) fprintf(stderr, "[gap batch] %zu jobs in %d group(s), widest %d sequences x %d columns: %zu B of LDS per wavefront, %d per CU, %lld slots\n", jobs.size(), n_groups, nmax, cap, lds, per_cu, (long long)slots);
+    if (timers && any_narrow) fprintf(stderr, "[gap batch] %zu jobs in %d group(s), widest %d sequences x %d columns: %zu B of LDS per wavefront, %d per CU, %lld slots\n", jobs.size(), n_groups, nmax, cap, lds, per_cu, (long long)slots);
+    // ---- the wide form: sized per launch by the jobs it is given.  Where things live: the fixed block (SharedWide) always in LDS;
+    // the rows (n x cap bytes) in LDS when they fit beside it, and the trace-back bytes (tb_bytes) too when both fit; what does not
+    // fit lies in the slot's workspace, which one wavefront re-reads out of L2.  No job is declined for its size in LDS.
+    // PM_GAP_WIDE_PLACE (measurements): 1 the trace-back bytes, 2 the rows, 3 both in the workspace whatever fits.
+    uint8_t* d_wide_ws = nullptr; size_t wide_ws_bytes = 0;
+    Job* d_again = nullptr; int32_t* d_again_cols = nullptr;      // the jobs of a second wide launch, and their column counts
+    const int place = getenv("PM_GAP_WIDE_PLACE") ? atoi(getenv("PM_GAP_WIDE_PLACE")) : 0;
+    struct Timed { hipEvent_t a, b; int form; };
+    std::vector<Timed> timed;
+    auto mark = [&](hipEvent_t* e) { hipError_t r = hipEventCreate(e); if (r == hipSuccess) { events.push_back(*e); r = hipEventRecord(*e, stream); } return r; };
+    auto launch_wide = [&](const Job* host_jobs, size_t nj, const Job* dev_jobs, int32_t* dev_cols, unsigned long long* counter) -> hipError_t {
+        int wn = 2, wc = 1;
+        for (size_t i = 0; i < nj; i++) { wn = std::max(wn, host_jobs[i].n); wc = std::max(wc, std::min<int>(host_jobs[i].max_cols, kWideCols)); }
+        auto r16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+        const size_t fixed = r16(sizeof(SharedWide)), rows_b = r16((size_t)wn * (size_t)wc), tb_b = r16(tb_bytes(wc));
+        bool rows_ws = (place & 2) != 0, tb_ws = (place & 1) != 0;
+        if (!rows_ws && fixed + rows_b > kLdsLimit) rows_ws = true;
+        if (!tb_ws && fixed + (rows_ws ? 0 : rows_b) + tb_b > kLdsLimit) tb_ws = true;
+        const size_t dyn = fixed + (rows_ws ? 0 : rows_b) + (tb_ws ? 0 : tb_b);
+        hipError_t e = hipFuncSetAttribute((const void*)gap_align_kernel<SharedWide>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
+        if (e != hipSuccess) return e;
+        const int wper_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / (dyn + 256)));
+        const int64_t wslots = std::min<int64_t>((int64_t)nj, (int64_t)prop.multiProcessorCount * wper_cu);
+        const size_t wstride = slot_bytes(wn, wc, kWideSeq, rows_ws, tb_ws);
+        if (wstride * (size_t)wslots > wide_ws_bytes) {
+            e = hipStreamSynchronize(stream);      // (an earlier launch may still use the smaller one)
+            if (e != hipSuccess) return e;
+            if (d_wide_ws) { (void)hipFree(d_wide_ws); owned.erase(std::find(owned.begin(), owned.end(), (void*)d_wide_ws)); d_wide_ws = nullptr; wide_ws_bytes = 0; }
+            e = dalloc(wstride * (size_t)wslots, (void**)&d_wide_ws);
+            if (e != hipSuccess) return e;
+            wide_ws_bytes = wstride * (size_t)wslots;
+        }
+        if (timers) fprintf(stderr, "[gap batch] wide form: %zu jobs, widest %d sequences x %d columns: %zu B of LDS per wavefront (rows in %s, trace-back in %s), %d per CU, %lld slots\n",
+                            nj, wn, wc, dyn, rows_ws ? "the workspace" : "LDS", tb_ws ? "the workspace" : "LDS", wper_cu, (long long)wslots);
+        Params P{dev_jobs, (int64_t)nj, d_off, d_chars, d_out, dev_cols, counter, d_wide_ws, (int64_t)wstride, wn, wc, rows_ws ? 1 : 0, tb_ws ? 1 : 0, dbg, d_prof};
+        Timed t{nullptr, nullptr, 1};
+        if (stats && (e = mark(&t.a)) != hipSuccess) return e;
+        hipLaunchKernelGGL(gap_align_kernel<SharedWide>, dim3((unsigned)wslots), dim3(64), dyn, stream, P);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if (stats) { if ((e = mark(&t.b)) != hipSuccess) return e; timed.push_back(t); }
+        return hipSuccess;
+    };
     std::vector<int32_t> got(jobs.size());
-    int signalled = 0;                 // groups whose completion the caller has been told
+    std::vector<Job> again; std::vector<size_t> again_at; std::vector<int32_t> again_got;
     for (int g = 0; g < n_groups; g++) {
-        const size_t j0 = first_of_group[(size_t)g], j1 = first_of_group[(size_t)g + 1];
+        const size_t j0 = first[(size_t)g * 2], jw = first[(size_t)g * 2 + 1], j1 = first[(size_t)g * 2 + 2];
         if (j1 > j0) {
-            // a group's jobs: their own queue counter, their slice of the job and column arrays; workspace and slots shared
-            Params P{d_jobs + j0, (int64_t)(j1 - j0), d_off, d_chars, d_out, d_cols + j0, d_next + g, d_ws, (int64_t)stride, nmax, cap, dbg, d_prof};
-            const int64_t gslots = std::min<int64_t>((int64_t)(j1 - j0), slots);
-            hipLaunchKernelGGL(gap_align_kernel, dim3((unsigned)gslots), dim3(64), rows_lds, stream, P);
-            GA_CHECK(hipGetLastError());
+            if (jw > j0) {
+                // a group's jobs: their own queue counter, their slice of the job and column arrays; workspace and slots shared
+                Params P{d_jobs + j0, (int64_t)(jw - j0), d_off, d_chars, d_out, d_cols + j0, d_next + 3 * g, d_ws, (int64_t)stride, nmax, cap, 0, 0, dbg, d_prof};
+                const int64_t gslots = std::min<int64_t>((int64_t)(jw - j0), slots);
+                Timed t{nullptr, nullptr, 0};
+                if (stats) GA_CHECK(mark(&t.a));
+                hipLaunchKernelGGL(gap_align_kernel<Shared>, dim3((unsigned)gslots), dim3(64), rows_lds, stream, P);
+                GA_CHECK(hipGetLastError());
+                if (stats) { GA_CHECK(mark(&t.b)); timed.push_back(t); }
+            }
+            if (j1 > jw) GA_CHECK(launch_wide(jobs.data() + jw, j1 - jw, d_jobs + jw, d_cols + jw, d_next + 3 * g + 1));
             // the rows of the group: the span of the output its jobs cover (a span may include rows of other groups: the
             // device buffer holds their final bytes if they are done, and they are copied again when they are not)
             int64_t lo = out_bytes, hi = 0;
             for (size_t i = j0; i < j1; i++) { lo = std::min(lo, jobs[i].row_off); hi = std::max(hi, jobs[i].row_off + (int64_t)jobs[i].n * jobs[i].max_cols); }
             GA_CHECK(hipMemcpyAsync(got.data() + j0, d_cols + j0, 4 * (j1 - j0), hipMemcpyDeviceToHost, stream));
+            if (wide) {
+                // what the narrow form declined although its rows may be wider than the narrow form's columns: once more, wide
+                GA_CHECK(hipStreamSynchronize(stream));
+                again.clear(); again_at.clear();
+                for (size_t i = j0; i < jw; i++) if (got[i] < 0 && jobs[i].max_cols > kMaxCols) { again.push_back(jobs[i]); again_at.push_back(i); }
+                if (!again.empty()) {
+                    if (!d_again) { GA_CHECK(dalloc(sizeof(Job) * jobs.size(), (void**)&d_again)); GA_CHECK(dalloc(4 * jobs.size(), (void**)&d_again_cols)); }
+                    GA_CHECK(hipMemcpyAsync(d_again, again.data(), sizeof(Job) * again.size(), hipMemcpyHostToDevice, stream));
+                    GA_CHECK(launch_wide(again.data(), again.size(), d_again, d_again_cols, d_next + 3 * g + 2));
+                    again_got.resize(again.size());
+                    GA_CHECK(hipMemcpyAsync(again_got.data(), d_again_cols, 4 * again.size(), hipMemcpyDeviceToHost, stream));
+                    GA_CHECK(hipStreamSynchronize(stream));
+                    for (size_t k = 0; k < again.size(); k++) { got[again_at[k]] = again_got[k]; if (stats && again_got[k] >= 0) { stats->jobs_wide++; stats->jobs_narrow--; } }
+                }
+            }
             if (hi > lo) GA_CHECK(hipMemcpyAsync(out_rows + lo, d_out + lo, (size_t)(hi - lo), hipMemcpyDeviceToHost, stream));
             GA_CHECK(hipStreamSynchronize(stream));
             for (size_t i = j0; i < j1; i++) cols[which[i]] = got[i];
+            if (stats) { for (size_t i = j0; i < jw; i++) stats->jobs_narrow += got[i] >= 0; for (size_t i = jw; i < j1; i++) stats->jobs_wide += got[i] >= 0; }
         }
         if (timers) { char what[32]; snprintf(what, sizeof what, "group %d", g + 1); lap(what); }
         if (done) done(ctx, g);
-        signalled = g + 1;
     }
-    (void)signalled;
+    for (const Timed& t : timed) { float ms = 0; if (hipEventElapsedTime(&ms, t.a, t.b) == hipSuccess) (t.form ? stats->ms_wide : stats->ms_narrow) += (double)ms; }
+    count_declined();
     if (d_prof) {
         unsigned long long prof[kProfStages];
         GA_CHECK(hipMemcpy(prof, d_prof, sizeof prof, hipMemcpyDeviceToHost));
@@ -993,5 +1164,31 @@ extern "C" int pm_gap_align_groups(int device, int64_t n_jobs, const int32_t* n_
     release();
     lap("release");
 #undef GA_CHECK
+    return PM_OK;
+}
+}  // namespace
+
+extern "C" int pm_gap_align_batch(int device, int64_t n_jobs, const int32_t* n_seqs, const int64_t* seq_off, const uint8_t* chars,
+                                  const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols) {
+    return align_groups(false, device, n_jobs, n_seqs, seq_off, chars, max_cols, row_off, out_rows, out_bytes, cols, 1, &n_jobs, nullptr, nullptr, nullptr);
+}
+// The same batch in groups of consecutive jobs (group g = jobs [group_end[g-1], group_end[g])): everything is uploaded once,
+// the groups are aligned one after the other, and when the rows and column counts of a group are in the caller's memory
+// `done(ctx, g)` is called (from this thread) -- the caller can start using them while the later groups are still running.
+extern "C" int pm_gap_align_groups(int device, int64_t n_jobs, const int32_t* n_seqs, const int64_t* seq_off, const uint8_t* chars,
+                                   const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols,
+                                   int n_groups, const int64_t* group_end, void (*done)(void* ctx, int group), void* ctx) {
+    return align_groups(false, device, n_jobs, n_seqs, seq_off, chars, max_cols, row_off, out_rows, out_bytes, cols, n_groups, group_end, done, ctx, nullptr);
+}
+// ... and with the wide form: the limits of pm_gap_limits(1, ...)
+extern "C" int pm_gap_align_groups_wide(int device, int64_t n_jobs, const int32_t* n_seqs, const int64_t* seq_off, const uint8_t* chars,
+                                        const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols,
+                                        int n_groups, const int64_t* group_end, void (*done)(void* ctx, int group), void* ctx, pm_gap_stats* stats) {
+    return align_groups(true, device, n_jobs, n_seqs, seq_off, chars, max_cols, row_off, out_rows, out_bytes, cols, n_groups, group_end, done, ctx, stats);
+}
+extern "C" int pm_gap_limits(int wide, int* max_seqs, int* max_seq_len, int* max_cols) {
+    if (max_seqs) *max_seqs = kMaxSeqs;
+    if (max_seq_len) *max_seq_len = wide ? kWideSeq : kMaxCols;
+    if (max_cols) *max_cols = wide ? kWideCols : kMaxCols;
     return PM_OK;
 }

@@ -437,6 +437,17 @@ private:
     std::vector<CacheEntry*> wanted_entries_;
 };
 
+// What the last write_output did with the gaps between adjacent MUMs that the reference hands to MUSCLE (PARSNP_TIMING: gap_*)
+struct GapCounts {
+    long jobs = 0;                 // gaps aligned
+    long jobs_wide = 0;            // ... of them with a string of more than 96 bases, wherever they were aligned
+    long longest = 0;              // bases of the longest gap string
+    long device_narrow = 0, device_wide = 0;      // aligned by the device's narrow / wide form
+    long host = 0;                 // aligned by the host restatement (gapalign.cpp)
+    double host_s = 0;             // ... in this many seconds, summed over the threads
+    double device_narrow_ms = 0, device_wide_ms = 0;      // kernel time of each form
+};
+extern GapCounts gap_counts;
 // XMFA + log (writeOutput).  gap_note: set when the gap aligner (gapalign.h) declined an inter-MUM gap and it was written '-'-padded.
 void write_output(Aligner& a, const std::string& stem, bool* gap_note);
 // parsnp.unalign (setUnalignableRegions); marks every base of the layout bitmaps.

@@ -128,7 +128,18 @@ void build_rows(const Aligner& a, const Lcb& ct, const std::vector<std::pair<siz
 }
 }  // namespace
 
+}  // namespace parsnp
+// The device gap aligner's wide form (include/parsnp_mum.h).  Weak: a provider of the ABI without it (the CPU providers of the
+// test builds, an older engine library) still links, and the writer then uses pm_gap_align_groups with its narrow limits.
+extern "C" int pm_gap_align_groups_wide(int device, int64_t n_jobs, const int32_t* n_seqs, const int64_t* seq_off, const uint8_t* chars,
+                                        const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols,
+                                        int n_groups, const int64_t* group_end, void (*done)(void* ctx, int group), void* ctx, pm_gap_stats* stats) __attribute__((weak));
+extern "C" int pm_gap_limits(int wide, int* max_seqs, int* max_seq_len, int* max_cols) __attribute__((weak));
+namespace parsnp {
+GapCounts gap_counts;
+
 void write_output(Aligner& a, const std::string& stem, bool* gap_note) {
+    gap_counts = GapCounts();
     using namespace std;
     const size_t n = a.n;
     const Params& prm = a.prm;
@@ -269,9 +280,13 @@ void write_output(Aligner& a, const std::string& stem, bool* gap_note) {
         return w;
     };
     // The gaps go to the device in ONE batch (pm_gap_align_batch: one wavefront per gap, include/parsnp_mum.h); the few the
-    // device does not take -- wider than its 96-column limit, or declined -- are aligned here by the host threads, the
-    // widest ones while the device works on the rest.  PARSNP_HOST_GAPS=1: everything on the host (measurement / tests).
-    constexpr unsigned kDeviceCols = 96;
+    // device does not take -- outside its limits (pm_gap_limits: 320 bases and 640 columns in its wide form, which covers every
+    // gap of the default d = 300), or declined -- are aligned here by the host threads, the widest ones while the device works on
+    // the rest.  PARSNP_HOST_GAPS=1: everything on the host (measurement / tests).
+    constexpr unsigned kNarrowCols = 96;                  // a gap with a longer string counts as wide (GapCounts::jobs_wide)
+    const bool wide_form = pm_gap_align_groups_wide != nullptr && pm_gap_limits != nullptr;
+    int dev_seqs = 512, dev_len = (int)kNarrowCols, dev_cols = (int)kNarrowCols;
+    if (wide_form) pm_gap_limits(1, &dev_seqs, &dev_len, &dev_cols);
     static const bool host_gaps = test_hook("PARSNP_HOST_GAPS") != nullptr;
     // The LCBs are cut into a few groups of consecutive LCBs with about the same alignment work, one device batch each:
     // the file offsets of a group's records only depend on the groups before it, so its records are written while the
@@ -297,15 +312,19 @@ void write_output(Aligner& a, const std::string& stem, bool* gap_note) {
     vector<int> group_of((size_t)nl, 0);
     for (size_t g = 0; g < ngroups; g++) for (size_t z = batch[g].z0; z < batch[g].z1; z++) group_of[z] = (int)g;
     for (long x = 0; x < nj; x++) jobs[(size_t)x].grp = group_of[jobs[(size_t)x].z];
-    if (!host_gaps && n <= 512) {
+    gap_counts.jobs = nj;
+    for (long x = 0; x < nj; x++) { gap_counts.jobs_wide += jobs[(size_t)x].max_len > kNarrowCols; gap_counts.longest = std::max<long>(gap_counts.longest, (long)jobs[(size_t)x].max_len); }
+    if (!host_gaps && n <= (size_t)dev_seqs) {
         int64_t out_bytes = 0;
         for (size_t g = 0; g < ngroups; g++) {               // group after group; the sorted order carries over: every group is longest first
             batch[g].y0 = B.job.size();
             for (long x = 0; x < nj; x++) {
                 Job& j = jobs[(size_t)x];
-                if (j.grp != (int)g || j.max_len > kDeviceCols) continue;
+                if (j.grp != (int)g || j.max_len > (unsigned)dev_len) continue;
                 j.dev = (long)B.job.size(); B.job.push_back(x);
-                const int32_t cap = (int32_t)std::min<unsigned>(kDeviceCols, j.max_len + j.max_len / 2 + 16);
+                // row capacity: half as much again as the longest string and a little (a job that needs more is declined and goes
+                // to the host); three quarters for the long ones, whose alignments reach 1.65 times their strings
+                const int32_t cap = (int32_t)std::min<unsigned>((unsigned)dev_cols, j.max_len > kNarrowCols ? j.max_len + (3 * j.max_len) / 4 + 16 : j.max_len + j.max_len / 2 + 16);
                 B.nseq.push_back((int32_t)n); B.maxcols.push_back(cap); B.rowoff.push_back(out_bytes);
                 out_bytes += (int64_t)n * cap;
             }
@@ -381,33 +400,38 @@ void write_output(Aligner& a, const std::string& stem, bool* gap_note) {
     for (auto& pr : batch_done) batch_ready.push_back(pr.get_future());
     const size_t on_device = B.job.size();
     struct Reported { vector<std::promise<int>>* done; size_t n = 0; } reported{&batch_done, 0};
+    pm_gap_stats device_stats{0, 0, 0, 0.0, 0.0};
     std::future<void> device_side = std::async(std::launch::async, [&] {
         int rc = PM_OK;
         if (!B.job.empty()) {
             vector<int64_t> group_end(ngroups);
             for (size_t g = 0; g < ngroups; g++) group_end[g] = (int64_t)batch[g].y1;
             const double t0 = clock_s();
-            rc = pm_gap_align_groups(-1, (int64_t)B.job.size(), B.nseq.data(), B.seqoff.data(), B.chars.data(), B.maxcols.data(), B.rowoff.data(),
-                                     B.out.data(), (int64_t)B.out.size(), B.cols.data(), (int)ngroups, group_end.data(),
-                                     [](void* ctx, int) { Reported* r = (Reported*)ctx; (*r->done)[r->n++].set_value(PM_OK); }, &reported);
+            auto report = [](void* ctx, int) { Reported* r = (Reported*)ctx; (*r->done)[r->n++].set_value(PM_OK); };
+            if (wide_form)
+                rc = pm_gap_align_groups_wide(-1, (int64_t)B.job.size(), B.nseq.data(), B.seqoff.data(), B.chars.data(), B.maxcols.data(), B.rowoff.data(),
+                                              B.out.data(), (int64_t)B.out.size(), B.cols.data(), (int)ngroups, group_end.data(), report, &reported, &device_stats);
+            else
+                rc = pm_gap_align_groups(-1, (int64_t)B.job.size(), B.nseq.data(), B.seqoff.data(), B.chars.data(), B.maxcols.data(), B.rowoff.data(),
+                                         B.out.data(), (int64_t)B.out.size(), B.cols.data(), (int)ngroups, group_end.data(), report, &reported);
             if (dbg) fprintf(stderr, "[output] gaps: device   %.4f s (%zu gaps in %zu groups)\n", clock_s() - t0, B.job.size(), ngroups);
         }
         while (reported.n < ngroups) batch_done[reported.n++].set_value(rc);      // (no device jobs, or a failure: the rest hears of it)
     });
-    vector<double> jt(dbg ? (size_t)nj : 0);
+    vector<double> jt((size_t)nj, 0.0);                    // host seconds per job
     auto host_align = [&](const vector<long>& which) {
         const long nw = (long)which.size();
 #pragma omp parallel for schedule(dynamic, 1) num_threads(threads)
         for (long y = 0; y < nw; y++) {
             const long x = which[(size_t)y];
             Job& j = jobs[(size_t)x];
-            const double t0 = dbg ? clock_s() : 0;
+            const double t0 = clock_s();
             gap_between(a, a.lcbs[j.z], j.t, &j.host);
             j.on_host = true;
             j.failed = !gap_align(j.host.seq, &j.host.aligned);
             if (!j.failed)                       // (rows of one alignment have one length; anything else is not printable here)
                 for (const string& r : j.host.aligned) if (r.size() != j.host.aligned[0].size()) { cerr << "parsnp_core: ragged gap alignment" << endl; exit(1); }
-            if (dbg) jt[(size_t)x] = clock_s() - t0;
+            jt[(size_t)x] = clock_s() - t0;
         }
     };
     vector<long> rest;
@@ -452,7 +476,14 @@ void write_output(Aligner& a, const std::string& stem, bool* gap_note) {
         vector<pair<size_t, Gap>> aligned;
         if (!pl.regular) {                                   // its gaps were not in the batch
             gaps_to_align(a, ct, &aligned);
+            const double t0 = clock_s();
             for (auto& tg : aligned) tg.second.failed = !gap_align(tg.second.seq, &tg.second.aligned);
+            long wide_here = 0, longest_here = 0;
+            for (auto& tg : aligned) { wide_here += tg.second.max_len > kNarrowCols; longest_here = std::max<long>(longest_here, (long)tg.second.max_len); }
+            const double spent = clock_s() - t0;
+#pragma omp critical(parsnp_gap_counts)
+            { gap_counts.jobs += (long)aligned.size(); gap_counts.host += (long)aligned.size(); gap_counts.jobs_wide += wide_here;
+              gap_counts.longest = std::max(gap_counts.longest, longest_here); gap_counts.host_s += spent; }
         } else {
             for (size_t t = 0; t < pl.gjob.size(); t++) {
                 if (pl.gjob[t] < 0) continue;
@@ -763,11 +794,17 @@ void write_output(Aligner& a, const std::string& stem, bool* gap_note) {
     if (map && munmap(map, (size_t)map_len) != 0) bad = 1;
     if (ftruncate(fd, (off_t)at) != 0 || close(fd) != 0 || bad) { cerr << "parsnp_core: error writing " << path << endl; exit(1); }
     for (char c : notes) if (c) *gap_note = true;
-    if (dbg && nj) {
-        double sum = 0, mx = 0; long arg = 0;
-        for (long x = 0; x < nj; x++) { sum += jt[(size_t)x]; if (jt[(size_t)x] > mx) { mx = jt[(size_t)x]; arg = x; } }
-        fprintf(stderr, "[output] %ld gap alignments: %zu on the device (%ld declined), %.3f s of host work, longest %.3f s (gap of %u columns)\n",
-                nj, on_device, declined, sum, mx, jobs[(size_t)arg].max_len);
+    {
+        double sum = 0, mx = 0; long arg = 0, on_host = 0;
+        for (long x = 0; x < nj; x++) { sum += jt[(size_t)x]; on_host += jobs[(size_t)x].on_host; if (jt[(size_t)x] > mx) { mx = jt[(size_t)x]; arg = x; } }
+        gap_counts.host += on_host; gap_counts.host_s += sum;
+        if (device_gaps_failed) device_stats = pm_gap_stats{0, 0, 0, 0.0, 0.0};
+        else if (!wide_form) device_stats.jobs_narrow = (int64_t)on_device - declined;      // (a provider without the wide form reports nothing)
+        gap_counts.device_narrow = (long)device_stats.jobs_narrow; gap_counts.device_wide = (long)device_stats.jobs_wide;
+        gap_counts.device_narrow_ms = device_stats.ms_narrow; gap_counts.device_wide_ms = device_stats.ms_wide;
+        if (dbg && nj)
+            fprintf(stderr, "[output] %ld gap alignments: %zu on the device (%lld narrow form in %.1f ms, %lld wide form in %.1f ms, %ld declined), %.3f s of host work, longest %.3f s (gap of %u columns)\n",
+                    nj, on_device, (long long)device_stats.jobs_narrow, device_stats.ms_narrow, (long long)device_stats.jobs_wide, device_stats.ms_wide, declined, sum, mx, jobs[(size_t)arg].max_len);
     }
     if (dbg) {
         long ns = 0, np = 0, nt = 0;

@@ -28,15 +28,58 @@ def random_genome(rng, n):
     return _BASES[rng.integers(0, 4, n)]
 
 
-def population(seed, n, n_genomes, div, indel_frac=0.0, sites=None, carry_seed=None, select=None):
+def _diverged_copy(rng, w, rate):
+    """an independently diverged copy of the window w (uint8 array): substitutions, insertions and deletions in equal parts at
+    `rate` in all, drawn again until its length is within 4 % of the window's -- the reference keeps a gap inside a cluster only
+    while the shortest gap string is at least 0.88 of the longest (src/parsnp.cpp:2693)"""
+    while True:
+        u = rng.random(len(w))
+        sub = (u >= rate / 3) & (u < 2 * rate / 3)
+        c = w.copy()
+        c[sub] = _alt(rng, w[sub])
+        keep = u >= rate / 3
+        ins = (u >= 2 * rate / 3) & (u < rate)
+        reps = np.ones(len(w), dtype=np.int64)
+        reps[ins] = 2
+        out = np.repeat(c[keep], reps[keep])
+        at = np.cumsum(reps[keep])[ins[keep]] - 1          # the inserted base follows its original
+        out[at] = _BASES[rng.integers(0, 4, len(at))]
+        if abs(len(out) - len(w)) <= 0.04 * len(w):
+            return out
+
+
+def population(seed, n, n_genomes, div, indel_frac=0.0, sites=None, carry_seed=None, select=None, windows=None):
     """-> (ref bytes, [genome bytes]) under the population model.  carry_seed: draw the genomes from a separate
     stream (same reference and site pool, different genomes -- one partition per rank in bench.py).  select: indices
     of the genomes to materialise (the random stream still advances over all of them, so genome i is the same bytes
-    whether or not its neighbours are built) -- one partition of BASELINE config 4 without building 2000 genomes."""
+    whether or not its neighbours are built) -- one partition of BASELINE config 4 without building 2000 genomes.
+    windows (default None: the sets are what they have always been): dict(count=, min_len=100, max_len=280, div=(0.15, 0.30),
+    haplotypes=None, flank=60) plants `count` hypervariable windows of min_len..max_len reference bases, evenly spread, in which
+    every genome -- or each of `haplotypes` haplotypes, dealt to the genomes at random -- carries an independently diverged copy
+    (_diverged_copy) at a rate drawn from `div`; `flank` bases on either side carry no segregating site, so that the flanks are
+    MUMs of one cluster and the window is a gap of 97 to about 290 bases between them (the gaps a default run, d = 300, hands
+    to the gap aligner on real genomes).  The windows draw from a stream of their own."""
     rng = np.random.default_rng(seed)
     ref = random_genome(rng, n)
     if sites is None:
         sites = np.flatnonzero(rng.random(n) < div)
+    win = []
+    if windows:
+        wr = np.random.default_rng([seed, 0x77696e64])
+        w = dict(dict(min_len=100, max_len=280, div=(0.15, 0.30), haplotypes=None, flank=60), **windows)
+        step = n // (w["count"] + 1)
+        assert step > w["max_len"] + 4 * w["flank"], "too many windows for this genome"
+        clear = np.zeros(n, dtype=bool)
+        for k in range(w["count"]):
+            length = int(wr.integers(w["min_len"], w["max_len"] + 1))
+            a = step * (k + 1) + int(wr.integers(0, step - length - 2 * w["flank"]))
+            clear[a - w["flank"]:a + length + w["flank"]] = True
+            rate = float(wr.uniform(*w["div"]))
+            nh = w["haplotypes"] or n_genomes
+            copies = [_diverged_copy(wr, ref[a:a + length], rate) for _ in range(nh)]
+            deal = wr.integers(0, nh, n_genomes) if w["haplotypes"] else np.arange(n_genomes)
+            win.append((a, length, copies, deal))
+        sites = sites[~clear[sites]]
     alt = _alt(rng, ref[sites])
     is_del = rng.random(len(sites)) < indel_frac
     if carry_seed is not None:
@@ -51,6 +94,14 @@ def population(seed, n, n_genomes, div, indel_frac=0.0, sites=None, carry_seed=N
         g[sub] = alt[carry & ~is_del]
         keep = np.ones(n, dtype=bool)
         keep[sites[carry & is_del]] = False
+        if win:
+            parts, prev = [], 0
+            for a, length, copies, deal in win:
+                parts += [g[prev:a][keep[prev:a]], copies[deal[gi]]]
+                prev = a + length
+            parts.append(g[prev:][keep[prev:]])
+            out.append(np.concatenate(parts).tobytes())
+            continue
         out.append(g[keep].tobytes())
     return ref.tobytes(), out
 
@@ -213,6 +264,9 @@ CONFIGS = {
     "bact200inv": ("pop_inverted", dict(seed=5, n=5_000_000, n_genomes=200, div=0.02, indel_frac=0.05, inv_every=20, inv_len=200_000)),
     "popinv12x400k": ("pop_inverted", dict(seed=31, n=400_000, n_genomes=12, div=0.02, indel_frac=0.05, inv_every=5, inv_len=30_000)),   # 2 of 12 genomes inverted: the reduced form, with a golden
     "bact2000": ("population", dict(seed=6, n=5_000_000, n_genomes=2000, div=0.02, indel_frac=0.05)),
+    # hypervariable windows: gaps of 97 to about 290 bases between adjacent MUMs, what the default d = 300 gives on real genomes
+    "hyper10x300k": ("population", dict(seed=41, n=300_000, n_genomes=10, div=0.01, indel_frac=0.05, windows=dict(count=160))),
+    "hyper200x200k": ("population", dict(seed=43, n=200_000, n_genomes=200, div=0.01, indel_frac=0.05, windows=dict(count=100, haplotypes=24))),
     "poprearr10x400k": ("pop_rearranged", dict(seed=13, n=400_000, n_genomes=10, div=0.05, frac=0.10)),
 }
 
