@@ -148,6 +148,11 @@ int64_t pm_result_table_id(const pm_result* r);
  *   "fast_tail"    0: a search whose rows stay on the device waits for its unit, candidate and accepted counts before it sizes the
  *                  launches that need them, as every other search does (default 1: capacities from the last call of the shape, the
  *                  kernels read the live counts, the counts come back with the results; the same result)
+ *   "hint_shrink"  N > 1: the capacities a "fast_tail" call takes from the same call of the last step (units, candidates, the seed
+ *                  regions' summaries) are divided by N (tests: the capacities are too small, the call repeats the part that
+ *                  needed them -- "tail_repeats" of pm_last_timing counts it -- and the result is the same; default 1)
+ *   "copy_kernel"  0: every download a call queues in front of a wait is a copy command of its own (rounds 1-6), instead of all of
+ *                  them leaving in one kernel launch that stores into page-locked host memory (default 1; the same bytes arrive)
  *   "atomic_marks" != 0: pm_store_settle marks the layout with atomic ORs even where the list's order allows plain stores (tests)
  *   "group_small"  0: the events of a recursion batch's small regions are found pair by pair and sorted with the others, instead of
  *                  once per distinct query piece (default 1; both give the same events, tests compare the two)
@@ -214,6 +219,11 @@ int pm_store_regions_equal(pm_session* s, const int32_t* a, const int32_t* b, in
 /* pm_multi_mum_batch on the rows of the listed regions; the candidates of region i become store rows
  * [*first_row + offsets[i], *first_row + offsets[i + 1]) (offsets[n + 1]). */
 int pm_store_search(pm_session* s, const int32_t* regions, const int32_t* minsize, int64_t n, int64_t* first_row, int64_t* offsets);
+/* The same with host work of the caller's that does not depend on the search: beside(ctx) is called exactly once, on the calling
+ * thread -- when the event search is queued and before the call first waits for the device, or on the way out of a call that never
+ * gets there (no region, an error).  It must not call the engine. */
+int pm_store_search_beside(pm_session* s, const int32_t* regions, const int32_t* minsize, int64_t n, int64_t* first_row, int64_t* offsets,
+                           void (*beside)(void*), void* ctx);
 /* One generation of doWork (:173-317).  The caller lists the waiting regions in the reference's order (reference start), with the
  * store rows of their candidates, cut into clusters (cluster c = regions [cluster_first[c], cluster_first[c + 1])) that it has
  * formed on the reference (maximal runs that overlap or touch there); the clusters are validated side by side, each in order: candidates settled against

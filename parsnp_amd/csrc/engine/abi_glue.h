@@ -190,6 +190,10 @@ int pm_store_search(pm_session* s, const int32_t* regions, const int32_t* minsiz
     if (!s || n < 0 || (n > 0 && (!regions || !minsize)) || !first_row || !offsets) return fail(PM_EINVAL, "bad argument");
     PM_STORE_CALL(s->engine->store_search(regions, minsize, n, first_row, offsets))
 }
+int pm_store_search_beside(pm_session* s, const int32_t* regions, const int32_t* minsize, int64_t n, int64_t* first_row, int64_t* offsets, void (*beside)(void*), void* ctx) {
+    if (!s || n < 0 || (n > 0 && (!regions || !minsize)) || !first_row || !offsets) { if (beside) beside(ctx); return fail(PM_EINVAL, "bad argument"); }
+    PM_STORE_CALL(s->engine->store_search(regions, minsize, n, first_row, offsets, beside, ctx))
+}
 int pm_store_validate(pm_session* s, const int32_t* regions, const int64_t* row_first, const int32_t* row_count, int64_t n_regions,
                       const int64_t* cluster_first, int64_t n_clusters, int32_t q, uint32_t* trouble, int64_t* n_children,
                       int64_t info_first, int64_t info_count, pm_row_info* info, int64_t stage_first, int32_t* second_stage_ran, int32_t generation, int32_t* done) {

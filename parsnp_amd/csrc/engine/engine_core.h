@@ -406,6 +406,10 @@ public:
         if (ord != (size_t)-1 && call_hints.size() <= ord) call_hints.resize(ord + 1);
         CallHint none;
         CallHint& hint = ord != (size_t)-1 ? call_hints[ord] : none;
+        if (hint_shrink > 1) {      // (tests) capacities carried over from the last step, made too small: the repeat paths run
+            if (hint.units > 0) hint.units = std::max<int64_t>(1, hint.units / hint_shrink);
+            if (hint.ncand > 0) hint.ncand = std::max<int64_t>(1, hint.ncand / hint_shrink);
+        }
         bool units_known = !gb;
         if (gb && !(fast_tail && hint.units > 0)) {
             be.d2h(&nunits, d_uoff.p + npairs, 8);
@@ -469,9 +473,11 @@ public:
                           SmallPairEvents{P, d_R.p, d_starts.p, d_lens.p, ngen, d_rep.p, d_evkey.p, d_evval.p, d_counter.p, (uint64_t)slice_cap, lbits, g_first, g_last, grouping ? d_gflag.p : nullptr});
             be.mark("sort");
             be.launch_wave("slice_offsets", 1, SliceOffsets{d_counter.p, d_sliceoff.p});
+            group_downloads();      // (the read-backs of this wait: one launch)
             be.d2h_async(qcounts.data(), d_qcount.p, 8 * qcounts.size());
             if (from_store) be.d2h_async(alg_sets, d_alg.p, sizeof alg_sets);
             if (!units_known) be.d2h_async(&nunits_live, d_uoff.p + npairs, 8);
+            run_beside();      // (the caller's host work that needs nothing of this call: the device is busy with the event search)
             be.d2h(counts.data(), d_counter.p, 8 * counts.size());            // round trip 1: event counts + error word (+ the queues' lengths, + the unit count)
             if (!units_known) {
                 units_known = true;
@@ -686,7 +692,7 @@ public:
             // -- accepted candidates, compacted on the device and downloaded straight into the result's blocks
             be.mark("compact");
             ensure(d_okcnt, (size_t)ncand + 1); ensure(d_okpos, (size_t)ncand + 1);
-            be.launch("ok_count", (int64_t)ncand + 1, OkCount{d_ok.p, ncand_p, d_okcnt.p});
+            be.launch("ok_count", (int64_t)ncand + 1, OkCount{d_ok.p, ncand_p, d_okcnt.p, (int64_t)ncand});
             be.exclusive_scan(d_okcnt.p, d_okpos.p, (size_t)ncand + 1);
             const int64_t* nok_p = d_okpos.p + ncand;      // the accepted count, where the device keeps it
             int64_t nok = 0;
@@ -698,13 +704,14 @@ public:
             out->release();
             out->kb = pool->take(4 * nokz); out->lonb = pool->take(4 * nokz);
             out->rows = want_rows; out->dirty_known = false; out->table_id = 0; out->store_base = -1;
-            const int64_t ms_before = ms_count, rg_before = rg_count, lay_before = layout_rows;
+            const int64_t ms_before = ms_count, rg_before = rg_count, lay_before = layout_rows, pkey_before = rg_pkey_init;
             bool anchor_call = false;
             if (!want_rows) {
                 ensure(d_csp, std::max<size_t>(nokz * nqz2, 1)); ensure(d_cfwd, std::max<size_t>(nokz * nqz2, 1));
                 be.launch("compact_sp", (int64_t)ncand * nq,
                           CompactSp{scand, d_ok.p, d_okpos.p, nq, d_ok_k.p, d_ok_lon.p, d_osp.p, d_ofwd.p, d_creg.p, d_ck.p, d_clon.p, d_csp.p, d_cfwd.p, ncand_p});
                 be.mark("download");
+                group_downloads();
                 out->spb = pool->take(4 * nokz * nqz2); out->fwdb = pool->take(nokz * nqz2);
                 be.d2h_async(out->spb.p, d_csp.p, 4 * nokz * nqz2);
                 be.d2h_async(out->fwdb.p, d_cfwd.p, nokz * nqz2);
@@ -718,7 +725,7 @@ public:
                 const bool to_store = anchor_call || keep_rows;
                 int32_t* p_start; uint8_t* p_strand; int32_t* p_lon; uint32_t* p_flags;
                 if (to_store) {
-                    if (anchor_call) { ms_count = 0; rg_count = 0; layout_rows = -1; }
+                    if (anchor_call) { ms_count = 0; rg_count = 0; layout_rows = -1; rg_pkey_init = 0; }      // (a new region store: none of its regions has been processed)
                     const size_t base = (size_t)ms_count, upto = base + nokz;
                     ensure_keep(d_anchor_start, std::max<size_t>(upto * ngz, 1), base * ngz); ensure_keep(d_ms_strand, std::max<size_t>(upto * ngz, 1), base * ngz);
                     ensure_keep(d_anchor_lon, std::max<size_t>(upto, 1), base); ensure_keep(d_anchor_flags, std::max<size_t>(upto, 1), base);
@@ -755,6 +762,7 @@ public:
                     if (anchor_call) out->table_id = ++table_counter;
                 }
                 be.mark("download");
+                group_downloads();      // (flags, lengths, regions, k and the two counts: one launch instead of seven copies)
                 out->flagsb = pool->take(4 * nokz);
                 be.d2h_async(out->flagsb.p, p_flags, 4 * nokz);
                 if (!keep_rows) {
@@ -769,13 +777,14 @@ public:
             be.d2h_async(out->kb.p, d_ck.p, 4 * nokz);
             int64_t counts_h[2] = {ncand_i, nok};
             if (!exact) { be.d2h_async(&counts_h[0], ncand_p, 8); be.d2h_async(&counts_h[1], nok_p, 8); }
+            flush_downloads();
             be.mark(nullptr);
             be.sync();                                                         // round trip 4: the results (and, where the call did not wait for them, the two counts)
             if (!exact) {
                 ncand_i = counts_h[0]; nok = counts_h[1];
                 const bool fits = (uint64_t)ncand_i <= ncand && anchor_call == (nreg == 1 && !gb && nok >= dirty_min);
                 if (!fits) {      // the capacity was too small, or the list is not the long list it was taken for: again, with the counts
-                    ms_count = ms_before; rg_count = rg_before; layout_rows = lay_before;
+                    ms_count = ms_before; rg_count = rg_before; layout_rows = lay_before; rg_pkey_init = pkey_before;
                     tail_repeats++;
                     be.mark("candidates");
                     continue;
@@ -954,8 +963,9 @@ public:
             be.launch_wave("seed_place", xcd_grid(rows), SeedPlace{S, L, P, d_list.p, nacc, d_sd_off.p, d_sd_keep.p, d_rg_start.p, d_rg_len.p, d_rg_info.p, (uint64_t)cap, rows});
             be.mark(nullptr);
             // the summaries travel with the count: as many as the last run had (a run with more fetches the rest)
-            const size_t guess = std::min(cap, rg_cap_hint);
+            const size_t guess = std::min(cap, rg_cap_hint / (size_t)hint_shrink);
             raw.resize(guess);
+            group_downloads();
             if (guess) be.d2h_async(raw.data(), d_rg_info.p, sizeof(RegInfo) * guess);
             if (!again) be.d2h_async(out, d_rowinfo.p, sizeof(RowInfo) * (size_t)rows);
             int64_t got = 0;
@@ -1045,7 +1055,14 @@ public:
     }
     // the multi-MUM search of regions of the store (pm_multi_mum_batch on their rows); the candidates become rows
     // [*first_row + off[i], *first_row + off[i + 1]) of the MUM store
-    int store_search(const int32_t* ids, const int32_t* minsize, int64_t n, int64_t* first_row, int64_t* off) {
+    // beside / beside_ctx: host work of the caller that does not depend on the search (pm_store_search_beside).  It runs once, on
+    // the calling thread, when the event search has been queued and before the call first waits for the device -- or, where the
+    // call returns without getting there, on the way out.  It must not call the engine.
+    void (*beside_fn)(void*) = nullptr; void* beside_ctx = nullptr;
+    void run_beside() { if (beside_fn) { void (*f)(void*) = beside_fn; beside_fn = nullptr; f(beside_ctx); } }
+    int store_search(const int32_t* ids, const int32_t* minsize, int64_t n, int64_t* first_row, int64_t* off, void (*beside)(void*) = nullptr, void* ctx = nullptr) {
+        beside_fn = beside; beside_ctx = ctx;
+        struct Always { Engine* e; ~Always() { e->run_beside(); } } on_every_way_out{this};
         if (!resident) { error = "the session is not in resident mode"; return -2; }
         std::vector<int64_t> rs((size_t)n), rl((size_t)n);
         for (int64_t i = 0; i < n; i++) {
@@ -1170,6 +1187,7 @@ public:
                                              d_ms_key.p, anchor_table_rows, (uint32_t*)(d_rg_count.p + 1), kOutwWaves});
             if (info_count > 0) be.launch("store_info", info_count, StoreInfoOut{store_view(), info_first, d_rowinfo.p});
             be.mark(nullptr);
+            group_downloads();
             if (info_count > 0) be.d2h_async(info, d_rowinfo.p, sizeof(RowInfo) * (size_t)info_count);
             be.d2h_async(&foreign_seen, d_foreign_count.p, 8);
             be.d2h_async(&outside_writes_call, d_outw_count.p, 8);
@@ -1512,6 +1530,7 @@ public:
     int64_t exact_cluster_tests = 0;      // generations validated with the exact test of their clusters (ClusterExtents ... ClusterDefer)
     int64_t deferred_regions = 0;         // regions a validation call left on the caller's work list (their cluster met an earlier one, or a child sorted first)
     bool clusters_out_of_order = false;   // a generation of this session failed the collinear test of its clusters: the exact test is asked at once from then on
+    int64_t hint_shrink = 1;              // (tests) divides the capacities a call takes from the same call of the last step (CallHint, the seed regions' summaries)
     bool phase_timing = true;             // HIP events around the phases of a call (pm_last_timing); off: the marks cost nothing
     bool tune(const std::string& key, int64_t value) {
         if (key == "flagged_div" && value >= 1) { flagged_div = value; return true; }
@@ -1532,6 +1551,8 @@ public:
         if (key == "work_budget" && value > 0) { work_budget = value; return true; }
         if (key == "dense_all") { dense_all = value != 0; return true; }
         if (key == "dirty_min" && value >= 0) { dirty_min = value; return true; }
+        if (key == "hint_shrink" && value >= 1) { hint_shrink = value; return true; }
+        if (key == "copy_kernel") { return tune_copy_kernel(be, value != 0, 0); }
         return false;
     }
 
@@ -1579,6 +1600,17 @@ private:
         b.raw = raw; b.p = (T*)raw; b.cap = want;
     }
     void collect_timing() { timing = be.collect(); }
+    // Downloads in one launch (HipBackend::d2h_group): the downloads queued from here to the call's next wait may leave together;
+    // flush_downloads() makes them leave now (where a phase of the call ends before the wait).  A backend without the grouping
+    // (the emulation: a download is a memcpy) copies one by one.
+    template <class T> static auto group_on(T& b, int) -> decltype(b.d2h_group(), void()) { b.d2h_group(); }
+    template <class T> static void group_on(T&, long) {}
+    template <class T> static auto flush_on(T& b, int) -> decltype(b.d2h_flush(), void()) { b.d2h_flush(); }
+    template <class T> static void flush_on(T&, long) {}
+    template <class T> static auto tune_copy_kernel(T& b, bool on, int) -> decltype(b.group_copies = on, true) { b.group_copies = on; return true; }
+    template <class T> static bool tune_copy_kernel(T&, bool, long) { return true; }
+    void group_downloads() { group_on(be, 0); }
+    void flush_downloads() { flush_on(be, 0); }
 
     SeqBlock* blk = nullptr; int64_t* d_goff = nullptr; int64_t* d_glen = nullptr;
     int64_t total_words = 0;

@@ -57,6 +57,31 @@ __global__ __launch_bounds__(256) void pm_fill_many(FillJobs jobs) {
     }
 }
 
+// several downloads in one launch: every job's bytes from device memory into page-locked host memory the device can address (the
+// backend's download ring), 64 KB per workgroup.  src is 4-byte aligned or copied byte by byte; dst is 256-byte aligned.
+struct CopyJobs { enum { kMax = 12 }; const void* src[kMax]; void* dst[kMax]; unsigned long long bytes[kMax]; unsigned int first_block[kMax + 1]; int n; };
+__global__ __launch_bounds__(256) void pm_copy_many(CopyJobs jobs) {
+    int j = 0;
+    while (j + 1 < jobs.n && blockIdx.x >= jobs.first_block[j + 1]) j++;
+    const unsigned long long off = (unsigned long long)(blockIdx.x - jobs.first_block[j]) << 16;
+    const unsigned long long n = jobs.bytes[j];
+    if (off >= n) return;
+    const unsigned long long len = n - off < 65536 ? n - off : 65536;
+    const unsigned char* s = (const unsigned char*)jobs.src[j] + off;
+    unsigned char* d = (unsigned char*)jobs.dst[j] + off;
+    unsigned long long done = 0;
+    if ((((uintptr_t)s) & 15) == 0) {
+        const unsigned long long n16 = len >> 4;
+        for (unsigned long long i = threadIdx.x; i < n16; i += 256) ((uint4*)d)[i] = ((const uint4*)s)[i];
+        done = n16 << 4;
+    } else if ((((uintptr_t)s) & 3) == 0) {
+        const unsigned long long n4 = len >> 2;
+        for (unsigned long long i = threadIdx.x; i < n4; i += 256) ((unsigned int*)d)[i] = ((const unsigned int*)s)[i];
+        done = n4 << 2;
+    }
+    for (unsigned long long i = done + threadIdx.x; i < len; i += 256) d[i] = s[i];
+}
+
 // one wavefront per work item: 64-thread workgroups, f.wave(item) with the lanes cooperating (shuffles, LDS)
 template <class F>
 __global__ __launch_bounds__(64) void pm_wave_kernel(F f, int64_t n) {
@@ -242,13 +267,44 @@ struct HipBackend {
     std::vector<Landing> landings;
     void land() { for (const Landing& l : landings) memcpy(l.dst, l.at, l.n); landings.clear(); dring_at = 0; }
     // at the start of every call of the C ABI: what an earlier call queued and never waited for (it returned an error) is forgotten
-    void drop_landings() { if (!landings.empty()) { (void)hipStreamSynchronize(stream); landings.clear(); dring_at = 0; } }
+    void drop_landings() { group.n = 0; group_blocks = 0; grouping = false; if (!landings.empty()) { (void)hipStreamSynchronize(stream); landings.clear(); dring_at = 0; } }
+    // The downloads a call queues in front of its wait are small and many (flags, lengths, regions, counts: seven at the end of a
+    // search), and every copy command is a dispatch of its own with ~10 us of idle device in front of it.  Between d2h_group() and
+    // the wait that follows (sync / d2h), downloads of up to kGroupMax bytes are collected instead and leave in ONE kernel launch
+    // that stores them into the ring (page-locked memory the device addresses; the wait makes the stores visible).
+    bool group_copies = true;      // pm_session_tune "copy_kernel"
+    bool grouping = false; CopyJobs group{}; unsigned int group_blocks = 0; uint8_t* dring_dev = nullptr;
+    static constexpr size_t kGroupMax = (size_t)4 << 20;
+    void d2h_group() { if (group_copies) grouping = true; }
+    void d2h_flush() { flush_group(); }      // (the launch now: where a phase of the call ends before its wait)
+    void flush_group() {
+        if (group.n) {
+            group.first_block[group.n] = group_blocks;
+            hipLaunchKernelGGL(pm_copy_many, dim3(group_blocks), dim3(256), 0, stream, group);
+            check(hipGetLastError(), "pm_copy_many");
+            group.n = 0; group_blocks = 0;
+        }
+    }
     void d2h_async(void* d, const void* s, size_t n) {
         const double t0 = copy_log() ? now_us() : 0;
         bytes_d2h += n;
         if (!n) return;
         const size_t need = (n + 255) & ~(size_t)255;
         if (!dring && hipHostMalloc((void**)&dring, kDRing, hipHostMallocDefault) != hipSuccess) dring = nullptr;
+        if (grouping && dring && !dring_dev) {      // the ring as the device addresses it (once); none: every download stays a copy
+            void* dp = nullptr;
+            if (hipHostGetDevicePointer(&dp, dring, 0) == hipSuccess && dp) dring_dev = (uint8_t*)dp; else { (void)hipGetLastError(); group_copies = false; grouping = false; }
+        }
+        if (grouping && dring && n <= kGroupMax && dring_at + need <= kDRing) {
+            if (group.n == CopyJobs::kMax) flush_group();
+            group.src[group.n] = s; group.dst[group.n] = dring_dev + dring_at; group.bytes[group.n] = n; group.first_block[group.n] = group_blocks;
+            group_blocks += (unsigned int)((n + 65535) >> 16);
+            group.n++;
+            landings.push_back(Landing{d, dring + dring_at, n});
+            dring_at += need;
+            if (copy_log()) fprintf(stderr, "[copy] d2h_group %9zu B\n", n);
+            return;
+        }
         if (dring && dring_at + need <= kDRing) {
             check(hipMemcpyAsync(dring + dring_at, s, n, hipMemcpyDeviceToHost, stream), "hipMemcpy D2H (ring)");
             landings.push_back(Landing{d, dring + dring_at, n});
@@ -265,7 +321,7 @@ struct HipBackend {
         d2h_async(d, s, n); sync();
         if (copy_log()) fprintf(stderr, "[copy] d2h       %9zu B %8.1f us (with the queued work before it)\n", n, now_us() - t0);
     }
-    void sync() { check(hipStreamSynchronize(stream), "hipStreamSynchronize"); land(); }
+    void sync() { flush_group(); grouping = false; check(hipStreamSynchronize(stream), "hipStreamSynchronize"); land(); }
     // an event on the engine's stream that any host thread may wait for (the slices of a row table in flight)
     void* event_record() {
         hipEvent_t e = nullptr;

@@ -1922,8 +1922,9 @@ struct FoldCandidates {
 
 // accepted candidates only, densely, in candidate order: what the host receives.  pos = exclusive prefix of ok.
 struct OkCount {
-    const uint8_t* ok; const int64_t* ncand; int64_t* cnt;     // launched over the capacity + 1: zeros past the live count close the scan
-    PM_HD void operator()(int64_t c) const { cnt[c] = c < *ncand ? (ok[c] ? 1 : 0) : 0; }
+    const uint8_t* ok; const int64_t* ncand; int64_t* cnt; int64_t cap;     // launched over the capacity + 1: zeros past the live count close the scan
+    // (ok[] holds `cap` candidates: a live count above the capacity -- the call repeats its tail then -- must not read past it)
+    PM_HD void operator()(int64_t c) const { cnt[c] = (c < *ncand && c < cap) ? (ok[c] ? 1 : 0) : 0; }
 };
 // tid = (candidate, query genome): the accepted candidates densely, as (sp, strand) per query genome (the documented
 // result of pm_multi_mum_batch; a session switched to MUM rows with pm_session_rows gets CompactCandidates instead)

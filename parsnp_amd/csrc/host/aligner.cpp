@@ -138,6 +138,11 @@ Aligner::Aligner(std::vector<Genome>& g, const Params& p, pm_session* session, A
     layout.resize(n);
     pool.swap(memory_->pool_store);      // the previous run's MUM records: capacity (and mapped pages) kept, see ~Aligner
     pool.clear();
+    {   // ... and the resident route's vectors, likewise (empty, capacity kept)
+        AlignerMemory::ResidentStore& rs = memory_->resident_store;
+        mums.swap(rs.mums); res_.start0.swap(rs.start0); res_.of_row.swap(rs.of_row); res_.len_of_row.swap(rs.len_of_row);
+        res_.found_key.swap(rs.found_key); res_.gen_info.swap(rs.gen_info); res_.gen_id.swap(rs.gen_id);
+    }
     gsize_.resize(n);
     for (size_t i = 0; i < n; i++) {
         if (genomes[i].seq.size() > (size_t)INT32_MAX - 64) fatal("genome longer than 2^31 bases: " + genomes[i].path);   // Mum rows are int32
@@ -186,6 +191,13 @@ Aligner::~Aligner() {
     auto lap = [&](const char* what) { if (dbg) { double u = now_s(); fprintf(stderr, "[release] %-10s %.4f s\n", what, u - t); t = u; } };
     cache_.clear(); lap("cache");
     pool.clear(); pool.swap(memory_->pool_store); lap("pool");
+    {
+        AlignerMemory::ResidentStore& rs = memory_->resident_store;
+        mums.clear(); res_.start0.clear(); res_.of_row.clear(); res_.len_of_row.clear(); res_.found_key.clear(); res_.gen_info.clear(); res_.gen_id.clear();
+        mums.swap(rs.mums); res_.start0.swap(rs.start0); res_.of_row.swap(rs.of_row); res_.len_of_row.swap(rs.len_of_row);
+        res_.found_key.swap(rs.found_key); res_.gen_info.swap(rs.gen_info); res_.gen_id.swap(rs.gen_id);
+        lap("lists");
+    }
     std::vector<Lcb>().swap(lcbs); lap("lcbs");
     own_memory_.reset(); lap("arenas");
 }

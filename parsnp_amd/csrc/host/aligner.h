@@ -292,6 +292,16 @@ struct AlignerMemory {
     std::vector<int64_t> batch_starts, batch_lens;   // run_batch's flat request arrays
     std::vector<pm_row_info> anchor_info_store;      // resident route: the block the anchors' per-row scalars arrive in, kept between runs (1.3 MB: not zero-filled per step)
     std::vector<Mum> pool_store, candidates;         // storage of Aligner::pool / validate_parallel's candidate records between runs
+    // resident route: the per-MUM and per-region vectors of a run (Aligner::mums, Resident::start0 ... below), a few MB that a step
+    // fills from empty.  Their storage is lent to the run and comes back cleared with ~Aligner: freed and allocated again, blocks of
+    // this size are mapped afresh and faulted in page by page in every step
+    struct ResidentStore {
+        std::vector<int> mums;
+        std::vector<int32_t> start0, of_row, len_of_row, gen_id;
+        std::vector<int64_t> found_key;
+        std::vector<pm_region_info> gen_info;
+        std::vector<pm_row_info> info;                // resident_extend: the scalars of the recursion's candidates, by store row (never zero-filled: a generation reads what its own call wrote)
+    } resident_store;
     std::vector<int> minlen_flat[2]; std::string minlen_expr[2];   // Aligner::min_length for lengths below 2^16, by expression (mums, anchors)
     // extend_generations: a candidate with a reverse-strand member outside its region, with the marks it saw in every genome's
     // interval and what was decided (engine/store_kernels.h: ForeignRead / ForeignBound)
@@ -334,6 +344,14 @@ public:
     const std::string& resident_why() const { return res_.why; }
     bool resident_chain();                               // phases C-D from the device (resident.cpp); false: the caller runs them
     void materialize();                                  // rows of the LCBs' MUMs (and the layout, for parsnp.unalign) for the writer; no-op on the host route
+    // After resident_chain() returned true `mums` and `lcbs` are NOT written yet: the device's answer is kept (Resident::chain_*)
+    // and the step report reads its counts from summary().  final_mums() / final_lcbs() write the lists on first use; whoever
+    // reads `mums` / `lcbs` of a finished run goes through them (or calls require_lists() where it takes the members directly).
+    struct Summary { long mums = 0, lcbs = 0, core_bp = 0; };
+    Summary summary() const;
+    const std::vector<int>& final_mums() { build_lists(); return mums; }
+    const std::vector<Lcb>& final_lcbs() { build_lists(); return lcbs; }
+    void require_lists(const char* who) const;           // fatal when the lists of a resident chain have not been written
     long key0(int idx) const { return res_.active ? (long)res_.start0[(size_t)idx] : (long)pool[(size_t)idx].start[0]; }      // reference start of a MUM
 
     bool find_anchors();       // returns m0 != 0
@@ -367,6 +385,11 @@ private:
         bool records_done = true;
         std::vector<int32_t> of_row, len_of_row;      // store row -> index of its MUM record in the pool (-1: none), and its length
         bool chain_queued = false;                                             // pm_store_chain_begin is in flight (resident_chain() collects it)
+        // the chain's answer, kept until someone asks for the lists (rows / heads: the engine's block, valid until the session's
+        // next pm_store_chain_begin -- a later step, on a later Aligner)
+        bool lists_pending = false;
+        pm_chain_info chain_info{}; const int32_t* chain_rows = nullptr; const uint8_t* chain_heads = nullptr;
+        Summary chain_summary;
         std::string chain_why;                                                 // why phases C-D fell back to the host's list logic
     } res_;
     bool resident_try_ = false;           // run_batch: ask for resident mode (the anchor call of the route)
@@ -375,6 +398,7 @@ private:
     bool resident_extend();
     void resident_chain_begin(size_t expect);
     void resident_records();
+    void build_lists();                   // mums / lcbs from the kept answer of the chain (no-op when they are written)
     void resident_verdicts();
     uint8_t resident_judge_rows(int cur, int back);
     void resident_fill_between();

@@ -84,8 +84,8 @@ static const char* step_report(pc_run* r, bool intervals) {
     // partition mode intersects across partitions (partition.py:35-61)
     o << ", \"lcb_ref_intervals\": [";
     bool first = true;
-    for (const Lcb& c : r->run.align->lcbs) {
-        if (!intervals) break;
+    static const std::vector<Lcb> none;
+    for (const Lcb& c : intervals ? r->run.align->final_lcbs() : none) {
         if (c.type != 1 || c.mums.empty()) continue;
         o << (first ? "" : ", ") << "[" << c.start[0] + 1 << ", " << c.end[0] << "]";
         first = false;

@@ -122,6 +122,7 @@ int CoreRun::open(const std::string& ini_path) {
     if (const char* v = test_hook("PM_CLUSTER_UNSURE")) (void)pm_session_tune(session, "cluster_unsure", atol(v));
     if (const char* v = test_hook("PM_CHAIN_TIE")) (void)pm_session_tune(session, "chain_tie", atol(v));
     if (const char* v = test_hook("PM_FAST_TAIL")) (void)pm_session_tune(session, "fast_tail", atol(v));
+    if (const char* v = test_hook("PM_HINT_SHRINK")) (void)pm_session_tune(session, "hint_shrink", atol(v));
     if (const char* v = test_hook("PM_TANGLE_ROUNDS")) (void)pm_session_tune(session, "tangle_rounds", atol(v));
     upload_s = now_s() - t1;
     return 0;
@@ -277,9 +278,8 @@ StepReport CoreRun::step_once(bool resident) {
     r.alg_bytes = s.alg_bytes; r.alg_bytes_kernel = s.alg_bytes_kernel; r.alg_bytes_query = s.alg_bytes_query; r.finder_calls = s.finder_calls; r.finder_regions = s.finder_regions; r.regions_processed = s.regions_processed;
     r.cache_hits = s.cache_hits; r.cache_misses = s.cache_misses; r.spec_rounds = s.spec_rounds;
     r.engine_ms = s.engine_ms; r.anchor_ms = s.anchor_ms; r.host = s;
-    r.anchors = a.m0; r.mums = (long)a.mums.size(); r.lcbs = (long)a.lcbs.size();
-    for (const Lcb& c : a.lcbs)
-        if (c.type == 1 && !c.mums.empty()) r.core_bp += c.end[0] - c.start[0];
+    const Aligner::Summary sm = a.summary();      // (a chain on the device: from its answer; the lists are written when the writer asks)
+    r.anchors = a.m0; r.mums = sm.mums; r.lcbs = sm.lcbs; r.core_bp = sm.core_bp;
     return r;
 }
 

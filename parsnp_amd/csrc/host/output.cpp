@@ -139,6 +139,7 @@ namespace parsnp {
 GapCounts gap_counts;
 
 void write_output(Aligner& a, const std::string& stem, bool* gap_note) {
+    a.require_lists("write_output");      // (CoreRun::write: materialize() writes them)
     gap_counts = GapCounts();
     using namespace std;
     const size_t n = a.n;
@@ -880,6 +881,7 @@ void write_output(Aligner& a, const std::string& stem, bool* gap_note) {
 // dropped), runs of one base are skipped, a trailing single character of the 80-column wrap is not printed, and the
 // coordinates are 0-based positions of the padded in-memory genome.
 void write_unaligned(Aligner& a) {
+    a.require_lists("write_unaligned");
     using namespace std;
     a.wait_layout();
     const size_t n = a.n;

@@ -20,8 +20,13 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <future>
 #include <iostream>
+
+// (an entry point a provider may lack -- the CPU checker's: the search then runs alone and the work beside it after it)
+extern "C" int pm_store_search_beside(pm_session* s, const int32_t* regions, const int32_t* minsize, int64_t n, int64_t* first_row, int64_t* offsets,
+                                      void (*beside)(void*), void* ctx) __attribute__((weak));
 
 namespace parsnp {
 
@@ -177,15 +182,23 @@ bool Aligner::resident_extend() {
     const double t0 = now_s();
     struct Records { Aligner* a; ~Records() { a->resident_records(); } } records_on_every_way_out{this};
     const bool dbg = getenv("PARSNP_DEBUG_TIMERS") != nullptr;
-    std::vector<pm_region_info> gen = std::move(res_.gen_info);
-    std::vector<int32_t> gen_id = std::move(res_.gen_id);
+    // (the work list and the candidates' scalars live in storage that outlasts the run: AlignerMemory::ResidentStore)
+    std::vector<pm_region_info> gen; std::vector<int32_t> gen_id;
+    gen.swap(res_.gen_info); gen_id.swap(res_.gen_id);
+    std::vector<pm_row_info> info;
+    info.swap(memory_->resident_store.info);
+    struct Storage { Aligner* a; std::vector<pm_region_info>* gen; std::vector<int32_t>* gen_id; std::vector<pm_row_info>* info;
+                     ~Storage() { gen->clear(); gen_id->clear(); gen->swap(a->res_.gen_info); gen_id->swap(a->res_.gen_id); info->swap(a->memory_->resident_store.info); } } storage_back{this, &gen, &gen_id, &info};
     // where the candidates of a region lie in the MUM store (-1: not searched yet), by region id
     std::vector<int64_t> row0; std::vector<int32_t> cnt;
     auto known = [&](int32_t id) { return (size_t)id < row0.size() && row0[(size_t)id] >= 0; };
-    std::vector<pm_row_info> info;
     struct Batch { int64_t first, total; };
     std::vector<Batch> batches;
-    auto search = [&](const std::vector<pm_region_info>& rs, const std::vector<int32_t>& ids) {      // one engine call for the regions without a result
+    // one engine call for the regions without a result.  beside: host work that needs nothing of the search, done while the device
+    // runs it (the engine calls back before its first wait) -- always the anchors' MUM records, which nothing before the commits reads
+    auto search = [&](const std::vector<pm_region_info>& rs, const std::vector<int32_t>& ids, const std::function<void()>& beside) {
+        struct Beside { Aligner* a; const std::function<void()>* more; bool ran; void run() { if (ran) return; ran = true; a->resident_records(); if (*more) (*more)(); } } bs{this, &beside, false};
+        struct Always { Beside* b; ~Always() { b->run(); } } on_every_way_out{&bs};
         std::vector<int32_t> want, mins;
         for (size_t i = 0; i < ids.size(); i++) {
             if (known(ids[i])) continue;
@@ -195,8 +208,10 @@ bool Aligner::resident_extend() {
         const double ts = now_s();
         std::vector<int64_t> off(want.size() + 1);
         int64_t first = 0;
-        const int rc = pm_store_search(session_, want.data(), mins.data(), (int64_t)want.size(), &first, off.data());
+        const int rc = pm_store_search_beside ? pm_store_search_beside(session_, want.data(), mins.data(), (int64_t)want.size(), &first, off.data(), [](void* p) { ((Beside*)p)->run(); }, &bs)
+                                              : pm_store_search(session_, want.data(), mins.data(), (int64_t)want.size(), &first, off.data());
         if (rc != PM_OK) engine_error("multi-MUM engine failed", rc);
+        if (dbg) fprintf(stderr, "[resident generation] search returned after %.6f s\n", now_s() - ts);
         for (size_t i = 0; i < want.size(); i++) {
             const size_t id = (size_t)want[i];
             if (row0.size() <= id) { row0.resize(id + 1, -1); cnt.resize(id + 1, 0); }
@@ -218,10 +233,18 @@ bool Aligner::resident_extend() {
     // where; a run that also lost a duplicate is noted (the reference erases ADJACENT duplicates only, and its unstable sort decides
     // what is adjacent).
     struct TieRun { size_t first, count; bool lost_duplicate; };
-    auto sort_unique = [&](const std::vector<pm_region_info>& in, const std::vector<int32_t>& in_id, std::vector<pm_region_info>* out, std::vector<int32_t>* out_id, std::vector<TieRun>* ties) {
-        std::vector<Handle> h(in.size());
-        for (size_t i = 0; i < in.size(); i++) h[i] = Handle{(long)in[i].ref_start, (int)i};
-        std::sort(h.begin(), h.end());
+    // (by_start: `in` by reference start, skipping its first `skip` entries -- the sort itself needs no engine call and may have been done
+    // beside a search)
+    auto by_start = [](const std::vector<pm_region_info>& in, size_t skip, std::vector<Handle>* h) {
+        h->resize(in.size() - skip);
+        for (size_t i = skip; i < in.size(); i++) (*h)[i - skip] = Handle{(long)in[i].ref_start, (int)(i - skip)};
+        std::sort(h->begin(), h->end());
+    };
+    auto sort_unique = [&](const std::vector<pm_region_info>& in, const std::vector<int32_t>& in_id, std::vector<pm_region_info>* out, std::vector<int32_t>* out_id, std::vector<TieRun>* ties, const std::vector<Handle>* sorted) {
+        std::vector<Handle> mine;
+        if (!sorted) { by_start(in, 0, &mine); sorted = &mine; }
+        const std::vector<Handle>& h = *sorted;
+        if (h.size() != in.size()) fatal("a work list was sorted for another generation");
         size_t run0 = out->size();
         bool lost = false;
         auto close_run = [&]() { if (out->size() - run0 > 1) ties->push_back(TieRun{run0, out->size() - run0, lost}); };
@@ -280,7 +303,9 @@ bool Aligner::resident_extend() {
         int64_t stage_first = 0;                      // > 0: the call holds two generations (pm_store_validate)
         std::vector<pm_region_info> rest; std::vector<int32_t> rest_id;
         if (gi == 0) {                  // the first pushed seed, before anything is sorted (:194-195 precede :291-292); every seed's search in ONE call
-            search(gen, gen_id);
+            std::vector<Handle> rest_sorted;      // the seeds after the first, by reference start: sorted beside their search
+            const bool presort = two_stages && gen.size() > 1;
+            search(gen, gen_id, [&] { if (presort) by_start(gen, 1, &rest_sorted); now.reserve(gen.size()); now_id.reserve(gen.size()); });
             lap("search call");
             now.push_back(gen.front()); now_id.push_back(gen_id.front());
             first = {0};
@@ -289,16 +314,16 @@ bool Aligner::resident_extend() {
             // does): the remaining seeds, sorted.  The device leaves them alone if it does
             if (two_stages && !gen.empty()) {
                 rest = gen; rest_id = gen_id;
-                sort_unique(gen, gen_id, &now, &now_id, &ties);
+                sort_unique(gen, gen_id, &now, &now_id, &ties, presort ? &rest_sorted : nullptr);
                 if (!settle_ties(&now, &now_id, ties)) return false;
                 cluster(now, 1, &first);
                 stage_first = 1;
                 gen.clear(); gen_id.clear();
             } else first.push_back(1);
         } else {
-            sort_unique(gen, gen_id, &now, &now_id, &ties);
+            sort_unique(gen, gen_id, &now, &now_id, &ties, nullptr);
             lap("sort");
-            search(now, now_id);
+            search(now, now_id, nullptr);
             if (!settle_ties(&now, &now_id, ties)) return false;
             cluster(now, 0, &first);
             gen.clear(); gen_id.clear();
@@ -466,6 +491,60 @@ bool Aligner::resident_chain() {
         return false;
     }
     if (ci.trouble & 2) fatal("inter-cluster region bookkeeping would overrun in the reference");
+    // The answer stays where the engine put it; what the step report needs -- the counts and the reference span of every LCB --
+    // takes one pass over the head flags and two rows per LCB.  The lists themselves (mums, lcbs: an index per MUM, three vectors
+    // per LCB) are written by build_lists() when someone reads them: the writer, beside its download of the rows.
+    if (ci.n_mums > ci.n_in || (ci.n_mums > 0 && !heads[0])) fatal("the device's MUM list does not begin with an LCB head, or is longer than the list it came from");
+    const std::vector<int32_t>& of = res_.of_row;
+    const int64_t top = (int64_t)of.size() - 1;
+    auto record = [&](int64_t z) {
+        const int32_t row = rows[z];
+        if (row < 0 || row > top || of[(size_t)row] < 0) fatal("the device's MUM list names a row the host does not hold");
+        return of[(size_t)row];
+    };
+    Summary sm;
+    int64_t nheads = 0;
+    for (int64_t x = 0; x < ci.n_mums;) {      // LCB by LCB: from a head to the MUM before the next one
+        int64_t y = x + 1;
+        for (uint64_t w; y + 8 <= ci.n_mums && (memcpy(&w, heads + y, 8), w == 0);) y += 8;      // (eight flags at a time)
+        while (y < ci.n_mums && !heads[y]) y++;
+        const int first = record(x), last = record(y - 1);
+        sm.core_bp += key0(last) + pool[(size_t)last].length - key0(first);
+        nheads++;
+        x = y;
+    }
+    if (nheads != ci.n_lcbs) fatal("the device's LCB count and its head flags differ");
+    sm.mums = (long)ci.n_mums; sm.lcbs = (long)(ci.n_fillers + ci.n_lcbs);
+    res_.chain_info = ci; res_.chain_rows = rows; res_.chain_heads = heads; res_.chain_summary = sm;
+    res_.lists_pending = true;
+    lcbs.clear();
+    filtered += ci.mums_dissolved; filtered_lcbs += ci.lcbs_dissolved;
+    unique_order = true;
+    stats.lcb_s += now_s() - t0;
+    if (dbg) fprintf(stderr, "[resident chain] with summary %.6f s\n", now_s() - t0);
+    stats.device_chain = 1;
+    return true;
+}
+
+// what the step report says about the run's lists
+Aligner::Summary Aligner::summary() const {
+    if (res_.lists_pending) return res_.chain_summary;
+    Summary sm;
+    sm.mums = (long)mums.size(); sm.lcbs = (long)lcbs.size();
+    for (const Lcb& c : lcbs)
+        if (c.type == 1 && !c.mums.empty()) sm.core_bp += c.end[0] - c.start[0];
+    return sm;
+}
+void Aligner::require_lists(const char* who) const {
+    if (res_.lists_pending) fatal(std::string(who) + " reads the MUM list of a chain on the device before it was written (Aligner::final_mums / final_lcbs)");
+}
+// mums and lcbs from the answer resident_chain() kept
+void Aligner::build_lists() {
+    if (!res_.lists_pending) return;
+    res_.lists_pending = false;
+    const double t0 = now_s();
+    const pm_chain_info& ci = res_.chain_info;
+    const int32_t* rows = res_.chain_rows; const uint8_t* heads = res_.chain_heads;
     // store row -> MUM record (res_.of_row: written with the records, beside phases C-D on the device)
     const std::vector<int32_t>& of = res_.of_row;
     const std::vector<int32_t>& len_of = res_.len_of_row;
@@ -474,7 +553,6 @@ bool Aligner::resident_chain() {
     lcbs.clear();
     lcbs.reserve((size_t)(ci.n_fillers + ci.n_lcbs));
     for (int64_t f = 0; f < ci.n_fillers; f++) { Lcb c; c.type = 0; c.length = 2; lcbs.push_back(std::move(c)); }      // (their rows: nothing reads them)
-    if (ci.n_mums > ci.n_in || (ci.n_mums > 0 && !heads[0])) fatal("the device's MUM list does not begin with an LCB head, or is longer than the list it came from");
     for (int64_t x = 0; x < ci.n_mums;) {      // LCB by LCB: from a head to the MUM before the next one
         int64_t y = x + 1;
         while (y < ci.n_mums && !heads[y]) y++;
@@ -496,12 +574,11 @@ bool Aligner::resident_chain() {
         x = y;
     }
     if ((int64_t)lcbs.size() != ci.n_fillers + ci.n_lcbs) fatal("the device's LCB count and its head flags differ");
-    filtered += ci.mums_dissolved; filtered_lcbs += ci.lcbs_dissolved;
-    unique_order = true;
-    stats.lcb_s += now_s() - t0;
-    if (dbg) fprintf(stderr, "[resident chain] with lists   %.6f s\n", now_s() - t0);
-    stats.device_chain = 1;
-    return true;
+    const Summary sm = res_.chain_summary;
+    long core = 0;
+    for (const Lcb& c : lcbs) if (c.type == 1) core += c.end[0] - c.start[0];
+    if ((long)mums.size() != sm.mums || (long)lcbs.size() != sm.lcbs || core != sm.core_bp) fatal("the lists of the chain differ from what the step reported");
+    if (getenv("PARSNP_DEBUG_TIMERS")) fprintf(stderr, "[resident chain] lists written %.6f s\n", now_s() - t0);
 }
 
 // setFinalClusters' test of MUM cur against the chain's last MUM, from rows fetched for the pair (a reverse-strand member,
@@ -585,12 +662,29 @@ void Aligner::materialize() {
     res_.materialized = true;
     const double t0 = now_s();
     std::vector<int32_t> rows; std::vector<int> who;
-    std::vector<uint8_t> seen(pool.size(), 0);
-    for (const Lcb& c : lcbs)
-        for (int idx : c.mums) if (!seen[(size_t)idx]) { seen[(size_t)idx] = 1; rows.push_back(pool[(size_t)idx].row); who.push_back(idx); }
-    int32_t* st = irows_.alloc(rows.size() * n + 1); uint8_t* fw = brows_.alloc(rows.size() * n + 1);
-    if (!rows.empty() && pm_store_rows(session_, rows.data(), 0, (int64_t)rows.size(), 0, st, fw) != PM_OK) engine_error("cannot fetch the MUM rows", PM_EHIP);
-    for (size_t i = 0; i < who.size(); i++) { pool[(size_t)who[i]].start = st + i * n; pool[(size_t)who[i]].fwd = fw + i * n; }
+    if (res_.lists_pending) {
+        // a chain on the device: the rows to fetch are its answer as it stands (every MUM of the list is in exactly one LCB), so the
+        // lists are written by a helper thread while this one waits for the download (the thread makes no engine call)
+        rows.assign(res_.chain_rows, res_.chain_rows + res_.chain_info.n_mums);
+        std::future<void> lists = std::async(std::launch::async, [this] { build_lists(); });
+        int32_t* st = irows_.alloc(rows.size() * n + 1); uint8_t* fw = brows_.alloc(rows.size() * n + 1);
+        const int rc = rows.empty() ? PM_OK : pm_store_rows(session_, rows.data(), 0, (int64_t)rows.size(), 0, st, fw);
+        lists.get();
+        if (rc != PM_OK) engine_error("cannot fetch the MUM rows", PM_EHIP);
+        if (mums.size() != rows.size()) fatal("the MUM list and the rows fetched for it differ");
+        for (size_t i = 0; i < rows.size(); i++) {
+            Mum& m = pool[(size_t)mums[i]];
+            if (m.row != rows[i]) fatal("the MUM list and the rows fetched for it differ");
+            m.start = st + i * n; m.fwd = fw + i * n;
+        }
+    } else {
+        std::vector<uint8_t> seen(pool.size(), 0);
+        for (const Lcb& c : lcbs)
+            for (int idx : c.mums) if (!seen[(size_t)idx]) { seen[(size_t)idx] = 1; rows.push_back(pool[(size_t)idx].row); who.push_back(idx); }
+        int32_t* st = irows_.alloc(rows.size() * n + 1); uint8_t* fw = brows_.alloc(rows.size() * n + 1);
+        if (!rows.empty() && pm_store_rows(session_, rows.data(), 0, (int64_t)rows.size(), 0, st, fw) != PM_OK) engine_error("cannot fetch the MUM rows", PM_EHIP);
+        for (size_t i = 0; i < who.size(); i++) { pool[(size_t)who[i]].start = st + i * n; pool[(size_t)who[i]].fwd = fw + i * n; }
+    }
     for (Lcb& c : lcbs) {
         if (c.type != 1 || c.mums.empty()) continue;
         const Mum& f = pool[(size_t)c.mums.front()]; const Mum& b = pool[(size_t)c.mums.back()];

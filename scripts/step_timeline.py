@@ -12,7 +12,7 @@ rows = list(c.execute("select name, start, end from %s order by start" % t))
 def short(n):
     m = re.search(r"pm_(?:wave_)?kernel<pm::(\w+)>", n)
     if m: return m.group(1)
-    m = re.search(r"(pm_fill16|pm_fill_many|gap_align_kernel|radix_sort\w*|onesweep\w*|scan\w*|copyBuffer|fillBuffer\w*)", n)
+    m = re.search(r"(pm_fill16|pm_fill_many|pm_copy_many|gap_align_kernel|radix_sort\w*|onesweep\w*|scan\w*|copyBuffer|fillBuffer\w*)", n)
     return m.group(1) if m else n.split("(")[0][-40:]
 idx = [i for i, (n, b, e) in enumerate(rows) if "IndexInsert" in n]
 big = max(rows[i][2] - rows[i][1] for i in idx)
