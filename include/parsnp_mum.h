@@ -369,6 +369,27 @@ int pm_gap_align_groups_wide(int device, int64_t n_jobs, const int32_t* n_seqs, 
  * pm_gap_align_groups_wide.  max_seqs: sequences of a job; max_seq_len: bases of a sequence; max_cols: columns of an
  * alignment.  Any pointer may be NULL.  Needs no device. */
 int pm_gap_limits(int wide, int* max_seqs, int* max_seq_len, int* max_cols);
+/* The same call with the device's tall form beside the other two: gaps of alignments with more than 512 genomes.  The three entry
+ * points above keep their limits exactly; this one takes every job within pm_gap_limits_tall: up to 2 048 sequences (2 000 genomes
+ * and the reference in one alignment) of up to 320 bases each whose intermediate alignments stay within 640 columns.  A job of at
+ * most 512 sequences runs exactly as in pm_gap_align_groups_wide (narrow or wide form, the second run included); a job of 513 to
+ * 2 048 sequences runs in the tall form -- the wide form's kernel with per-sequence arrays of 2 048 entries, its rows in the device
+ * workspace when they do not fit the LDS; per group the tall jobs are launched after the wide ones, longest first, on as many
+ * slots as 8 GiB of workspace allow (a slot of 2 048 sequences needs 20 MB).
+ *   cols[j] = -1   only: fewer than 2 or more than 2 048 sequences, a sequence that is empty or longer than 320 bases, an
+ *                  intermediate alignment wider than 640 columns or than max_cols[j], a lower-case letter or a 'U', or a case in
+ *                  which MUSCLE itself quits.
+ * stats (may be NULL): what the call did; a record of its own, pm_gap_stats keeps its size. */
+typedef struct pm_gap_tall_stats {
+    int64_t jobs_narrow, jobs_wide, jobs_tall;   /* jobs aligned by each form */
+    int64_t declined;                            /* jobs answered with cols = -1 */
+    double ms_narrow, ms_wide, ms_tall;          /* kernel time of each form, summed over the launches (HIP events) */
+} pm_gap_tall_stats;
+int pm_gap_align_groups_tall(int device, int64_t n_jobs, const int32_t* n_seqs, const int64_t* seq_off, const uint8_t* chars,
+                             const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols,
+                             int n_groups, const int64_t* group_end, void (*done)(void* ctx, int group), void* ctx, pm_gap_tall_stats* stats);
+/* The limits of pm_gap_align_groups_tall (2 048 sequences, 320 bases, 640 columns).  Any pointer may be NULL.  Needs no device. */
+int pm_gap_limits_tall(int* max_seqs, int* max_seq_len, int* max_cols);
 
 /* Device-side timing of the last pm_multi_mum_batch on this session (HIP events on the engine's stream):
  * names[i] / ms[i] for i < *count (count in: capacity, out: filled).  Used by bench.py's roofline line.

@@ -1,5 +1,5 @@
-// gapalign_hip.hip -- the inter-MUM gap aligner on the MI355X: pm_gap_align_batch, pm_gap_align_groups and
-// pm_gap_align_groups_wide (include/parsnp_mum.h).
+// gapalign_hip.hip -- the inter-MUM gap aligner on the MI355X: pm_gap_align_batch, pm_gap_align_groups,
+// pm_gap_align_groups_wide and pm_gap_align_groups_tall (include/parsnp_mum.h).
 //
 // Replaces, for a whole run's worth of gaps at once, what the reference's XMFA writer does gap by gap:
 // MuscleInterface::CallMuscleFast (src/MuscleInterface.cpp:37-78, called at src/parsnp.cpp:854-855), i.e. the one
@@ -23,10 +23,13 @@
 //   merge        aligngivenpath.cpp:124-366                 rows re-spelled through a column map, lanes over columns
 // A job the device declines (more than kMaxSeqs sequences, an alignment wider than its row capacity or kMaxCols, an
 // empty sequence, MUSCLE's own "quit" conditions) is reported with cols = -1 and stays with the caller's host path.
-// Two forms of the one kernel, a template over the limits (SharedT): the narrow form (kMaxCols = 96 bases and columns; rows and
+// Three forms of the one kernel, a template over the limits (SharedT): the narrow form (kMaxCols = 96 bases and columns; rows and
 // trace-back bytes in LDS) and the wide form (kWideSeq = 320 bases, kWideCols = 640 columns: every gap of the reference's default
 // d = 300; rows in LDS when they fit, else -- like its trace-back bytes -- in the slot's workspace).  The first two entry points run
-// the narrow form alone, with the limits they have always had; the third splits its jobs by form (align_groups).
+// the narrow form alone, with the limits they have always had; the third splits its jobs by form (align_groups).  Both take up to
+// kMaxSeqs = 512 sequences.  The tall form (kTallSeqs = 2 048 sequences with the wide form's columns: one alignment of 2 000 genomes
+// and the reference) is the wide form with its per-sequence arrays four times as long; its rows never fit the LDS, and its slots
+// are bounded by the workspace they need (kTallWorkspace).  The fourth entry point adds it to what the third does.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -43,7 +46,9 @@
 
 namespace {
 
-constexpr int kMaxSeqs = 512;      // sequences per alignment on the device
+constexpr int kMaxSeqs = 512;      // sequences per alignment on the device: narrow and wide form
+constexpr int kTallSeqs = 2048;    // ... and in the tall form (columns and bases: those of the wide form)
+constexpr size_t kTallWorkspace = (size_t)8 << 30;      // bytes of slot workspace a tall launch may ask for (a slot of 2 048 sequences needs 20 MB)
 constexpr int kMaxCols = 96;       // narrow form: bases of a sequence and columns of any intermediate alignment (LDS per wavefront ~25 KB: 6 alignments in flight per CU)
 constexpr int kWideSeq = 320;      // wide form: bases of a sequence (every gap the default d = 300 of the reference's driver can produce) ...
 constexpr int kWideCols = 640;     // ... and columns of any intermediate alignment (300-base strings align to about 1.65 times their length)
@@ -138,13 +143,14 @@ __device__ inline void wave_argmin(float& v, unsigned& i) {
 // LDS of the one wavefront of a workgroup, used phase after phase (the alignment rows themselves -- n rows of `cap`
 // bytes, row p = leaf p in the order of the root alignment -- follow it as dynamic LDS: every profile is a sequential
 // sum over its rows, 20 000 row visits for 201 sequences, and from global memory each visit is a round trip)
-// kCols_: columns of an alignment, kSeq_: bases of a sequence -- (kMaxCols, kMaxCols) is the narrow form, (kWideCols, kWideSeq) the wide one
-template <int kCols_, int kSeq_>
+// kCols_: columns of an alignment, kSeq_: bases of a sequence, kSeqs_: sequences -- (kMaxCols, kMaxCols, kMaxSeqs) is the narrow form,
+// (kWideCols, kWideSeq, kMaxSeqs) the wide one, (kWideCols, kWideSeq, kTallSeqs) the tall one
+template <int kCols_, int kSeq_, int kSeqs_>
 struct __align__(16) SharedT {
-    static constexpr int kCols = kCols_, kSeq = kSeq_;
+    static constexpr int kCols = kCols_, kSeq = kSeq_, kSeqs = kSeqs_;
     using col_t = typename std::conditional<(kCols_ > 255), uint16_t, uint8_t>::type;      // a column count / a sequence length
   union {           // the guide tree is finished (and synchronised on) before the first profile is built
-    struct { float mind[kMaxSeqs]; unsigned nearest[kMaxSeqs]; unsigned node[kMaxSeqs]; float height[kMaxSeqs]; } t;      // tree
+    struct { float mind[kSeqs_]; unsigned nearest[kSeqs_]; unsigned node[kSeqs_]; float height[kSeqs_]; } t;      // tree
     struct {
             float fa[4][kCols]; uint8_t orda[kCols]; float opena[kCols], closea[kCols];   // profile A: sorted counts, their letters
             float sb[4][kCols]; float openb[kCols], closeb[kCols];                           // profile B: scores per letter
@@ -160,15 +166,16 @@ struct __align__(16) SharedT {
     static_assert(3 * 4 * (kCols_ + 2) + (kCols_ + 2) + 2 * (2 * kCols_ + 2) + 4 * (2 * kCols_ + 2) >= 6 * 4 * kCols_, "the sums fit");
     __device__ float& acc(int kind, int c) { if constexpr (kCols_ <= 128) return p.acc[kind][c]; else return p.bD[kind * kCols_ + c]; }
     uint8_t letter[256];       // alpha.cpp:125-166 (c_letter, copied: a table in constant memory costs a trip to memory per lane)
-    float total_i[kMaxSeqs];   // per internal node: sequential float sum of the weights of its rows, in row order
-    col_t ncols_i[kMaxSeqs];   // per internal node: columns of its alignment
-    col_t rowlen[kMaxSeqs];    // length of the sequence in row p
+    float total_i[kSeqs_];   // per internal node: sequential float sum of the weights of its rows, in row order
+    col_t ncols_i[kSeqs_];   // per internal node: columns of its alignment
+    col_t rowlen[kSeqs_];     // length of the sequence in row p
     uint16_t codes[kSeq];
-    float wrow[kMaxSeqs];      // weight of the sequence in row p (rows = leaves in the order of the root alignment)
+    float wrow[kSeqs_];        // weight of the sequence in row p (rows = leaves in the order of the root alignment)
     int32_t flag;
 };
-using Shared = SharedT<kMaxCols, kMaxCols>;
-using SharedWide = SharedT<kWideCols, kWideSeq>;
+using Shared = SharedT<kMaxCols, kMaxCols, kMaxSeqs>;
+using SharedWide = SharedT<kWideCols, kWideSeq, kMaxSeqs>;
+using SharedTall = SharedT<kWideCols, kWideSeq, kTallSeqs>;
 
 // ---- profile of the alignment held by rows [lo, lo+ns) (nc columns) -> either the A arrays or the B arrays
 // R: the rows in LDS.  Each of a column's six sums runs over the rows one after the other (float: the order is part of the
@@ -417,7 +424,7 @@ __device__ bool align_job(Sh& S, uint8_t* R, uint8_t* TB, const Slot& W, const P
     const int n = job.n, cap = P.cap;
     unsigned long long prof_acc[kProfStages] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long prof_t0 = (kGapClocks && P.prof) ? (unsigned long long)clock64() : 0;
-    if (n < 2 || n > kMaxSeqs) return false;
+    if (n < 2 || n > Sh::kSeqs) return false;
     // ---- sequences: lengths, FixAlpha (seq.cpp:331-344) happens when the rows are filled
     int bad = 0, wild = 0;
     for (int i = lane; i < n; i += 64) {
@@ -561,7 +568,7 @@ __device__ bool align_job(Sh& S, uint8_t* R, uint8_t* TB, const Slot& W, const P
         if (rmin == kNone || rmin >= un) return false;
         // the distances of this step are requested together (two per cluster and lane, plus the pair's own): one round
         // trip to the workspace per merge instead of one per 64 clusters
-        constexpr int kRounds = kMaxSeqs / 64;
+        constexpr int kRounds = Sh::kSeqs / 64;      // (the tall form: 2 x 32 registers of distances per lane, no scratch)
         float dl[kRounds], dr[kRounds];
         const float dlr = W.dist[tri(lmin, rmin)];
 #pragma unroll
@@ -926,14 +933,16 @@ extern "C" int64_t pm_gap_debug_peek(int32_t* out, int64_t cap) {
 }
 
 namespace {
-// One call of any of the three entry points.  wide = false: pm_gap_align_batch / pm_gap_align_groups, the narrow form alone, with the
-// limits and the launch they have always had.  wide = true: pm_gap_align_groups_wide -- a job with a sequence of more than kMaxCols
+// One call of any of the four entry points.  level = 0: pm_gap_align_batch / pm_gap_align_groups, the narrow form alone, with the
+// limits and the launch they have always had.  level = 1: pm_gap_align_groups_wide -- a job with a sequence of more than kMaxCols
 // bases goes to the wide form, and a job the narrow form declined whose rows may be wider than kMaxCols is run again in the wide
-// form before its group is reported.
-int align_groups(bool wide, int device, int64_t n_jobs, const int32_t* n_seqs, const int64_t* seq_off, const uint8_t* chars,
+// form before its group is reported.  level = 2: pm_gap_align_groups_tall -- the same, and a job of more than kMaxSeqs sequences
+// goes to the tall form (which has the wide form's columns: nothing it declines would fare better in a second run).
+int align_groups(int level, int device, int64_t n_jobs, const int32_t* n_seqs, const int64_t* seq_off, const uint8_t* chars,
                  const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols,
-                 int n_groups, const int64_t* group_end, void (*done)(void* ctx, int group), void* ctx, pm_gap_stats* stats) {
-    if (stats) *stats = pm_gap_stats{0, 0, 0, 0.0, 0.0};
+                 int n_groups, const int64_t* group_end, void (*done)(void* ctx, int group), void* ctx, pm_gap_tall_stats* stats) {
+    const bool wide = level >= 1;
+    if (stats) *stats = pm_gap_tall_stats{0, 0, 0, 0, 0.0, 0.0, 0.0};
     if (n_jobs < 0 || (n_jobs > 0 && (!n_seqs || !seq_off || !chars || !max_cols || !row_off || !out_rows || !cols))) return fail(PM_EINVAL, "bad argument");
     if (n_groups < 1 || !group_end || group_end[n_groups - 1] != n_jobs) return fail(PM_EINVAL, "bad job groups");
     for (int g = 0; g < n_groups; g++) if (group_end[g] < (g ? group_end[g - 1] : 0)) return fail(PM_EINVAL, "bad job groups");
@@ -968,23 +977,23 @@ int align_groups(bool wide, int device, int64_t n_jobs, const int32_t* n_seqs, c
         }
         GA_CHECK(table_err);
     }
-    // jobs the device takes, per group the narrow ones and then the wide ones, each longest first (the cost of one alignment grows
-    // with the square of its width)
+    // jobs the device takes, per group the narrow ones, then the wide ones, then the tall ones, each longest first (the cost of one
+    // alignment grows with the square of its width)
     std::vector<Job> jobs; std::vector<int64_t> which; std::vector<int> group_of_job, form_of_job;
     int64_t seq = 0, total_chars = 0;
     int nmax = 2, cap = 1;             // of the narrow form: the widest job of the call
     std::vector<int> widest((size_t)n_jobs, 0);
-    const int seq_limit = wide ? kWideSeq : kMaxCols;
+    const int seq_limit = wide ? kWideSeq : kMaxCols, seqs_limit = level >= 2 ? kTallSeqs : kMaxSeqs;
     int grp = 0;
     for (int64_t j = 0; j < n_jobs; j++) {
         while (grp + 1 < n_groups && j >= group_end[grp]) grp++;
         cols[j] = -1;
         const int n = n_seqs[j];
-        int w = 0; bool ok = n >= 2 && n <= kMaxSeqs && max_cols[j] >= 1;
+        int w = 0; bool ok = n >= 2 && n <= seqs_limit && max_cols[j] >= 1;
         for (int i = 0; i < n && ok; i++) { const int64_t L = seq_off[seq + i + 1] - seq_off[seq + i]; if (L <= 0 || L > seq_limit) ok = false; else w = std::max<int>(w, (int)L); }
         if (ok && row_off[j] + (int64_t)n * max_cols[j] > out_bytes) ok = false;
         if (ok) {
-            const int form = w > kMaxCols ? 1 : 0;
+            const int form = n > kMaxSeqs ? 2 : (w > kMaxCols ? 1 : 0);
             jobs.push_back(Job{seq, n, max_cols[j], row_off[j]}); which.push_back(j); group_of_job.push_back(grp); form_of_job.push_back(form); widest[(size_t)j] = w;
             if (!form) { nmax = std::max(nmax, n); cap = std::max(cap, std::min<int>(max_cols[j], kMaxCols)); }
         }
@@ -993,8 +1002,9 @@ int align_groups(bool wide, int device, int64_t n_jobs, const int32_t* n_seqs, c
     total_chars = seq_off[seq];
     auto count_declined = [&]() { if (stats) { stats->declined = 0; for (int64_t j = 0; j < n_jobs; j++) stats->declined += cols[j] < 0; } };
     if (jobs.empty()) { count_declined(); all_done(0); return PM_OK; }
-    // in the sorted job list: group g = [first[2g], first[2g+2]), its narrow jobs first, its wide jobs from first[2g+1]
-    std::vector<size_t> first((size_t)n_groups * 2 + 1, 0);
+    // in the sorted job list: group g = [first[3g], first[3g+3]), its narrow jobs first, its wide jobs from first[3g+1], its tall
+    // jobs from first[3g+2]
+    std::vector<size_t> first((size_t)n_groups * 3 + 1, 0);
     {
         std::vector<size_t> order(jobs.size());
         for (size_t i = 0; i < order.size(); i++) order[i] = i;
@@ -1004,8 +1014,8 @@ int align_groups(bool wide, int device, int64_t n_jobs, const int32_t* n_seqs, c
             return widest[(size_t)which[a]] > widest[(size_t)which[b]];
         });
         std::vector<Job> j2; std::vector<int64_t> w2;
-        for (size_t i : order) { j2.push_back(jobs[i]); w2.push_back(which[i]); first[(size_t)group_of_job[i] * 2 + (size_t)form_of_job[i] + 1]++; }
-        for (size_t k = 0; k < (size_t)n_groups * 2; k++) first[k + 1] += first[k];
+        for (size_t i : order) { j2.push_back(jobs[i]); w2.push_back(which[i]); first[(size_t)group_of_job[i] * 3 + (size_t)form_of_job[i] + 1]++; }
+        for (size_t k = 0; k < (size_t)n_groups * 3; k++) first[k + 1] += first[k];
         jobs.swap(j2); which.swap(w2);
     }
     const bool timers = getenv("PARSNP_DEBUG_TIMERS") != nullptr;
@@ -1017,7 +1027,7 @@ int align_groups(bool wide, int device, int64_t n_jobs, const int32_t* n_seqs, c
     GA_CHECK(hipGetDeviceProperties(&prop, device));
     GA_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     auto dalloc = [&](size_t bytes, void** p) { hipError_t e = hipMalloc(p, bytes ? bytes : 1); if (e == hipSuccess) owned.push_back(*p); return e; };
-    const bool any_narrow = [&] { for (int g = 0; g < n_groups; g++) if (first[(size_t)g * 2 + 1] > first[(size_t)g * 2]) return true; return false; }();
+    const bool any_narrow = [&] { for (int g = 0; g < n_groups; g++) if (first[(size_t)g * 3 + 1] > first[(size_t)g * 3]) return true; return false; }();
     // ---- the narrow form.  LDS of a workgroup: the fixed block plus the alignment rows of the widest job and the trace-back bytes;
     // as many workgroups per CU as fit in 160 KB
     constexpr size_t kLdsLimit = 160 * 1024 - 1024;
@@ -1030,7 +1040,7 @@ int align_groups(bool wide, int device, int64_t n_jobs, const int32_t* n_seqs, c
         if (lds > 64 * 1024) GA_CHECK(hipFuncSetAttribute((const void*)gap_align_kernel<Shared>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rows_lds));
         per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / (lds + 256)));
         size_t most = 0;      // narrow jobs of one group (without a wide job in the call: of the call, as the launch has always been sized)
-        for (int g = 0; g < n_groups; g++) most = std::max(most, first[(size_t)g * 2 + 1] - first[(size_t)g * 2]);
+        for (int g = 0; g < n_groups; g++) most = std::max(most, first[(size_t)g * 3 + 1] - first[(size_t)g * 3]);
         slots = std::min<int64_t>(wide ? (int64_t)most : (int64_t)jobs.size(), (int64_t)prop.multiProcessorCount * per_cu);
         stride = slot_bytes(nmax, cap, kMaxCols, false, false);
     }
@@ -1040,12 +1050,12 @@ int align_groups(bool wide, int device, int64_t n_jobs, const int32_t* n_seqs, c
     GA_CHECK(dalloc((size_t)total_chars, (void**)&d_chars));
     GA_CHECK(dalloc((size_t)out_bytes, (void**)&d_out));
     GA_CHECK(dalloc(4 * jobs.size(), (void**)&d_cols));
-    GA_CHECK(dalloc(8 * 3 * (size_t)n_groups, (void**)&d_next));      // a queue counter per launch: narrow, wide, wide again
+    GA_CHECK(dalloc(8 * 4 * (size_t)n_groups, (void**)&d_next));      // a queue counter per launch: narrow, wide, wide again, tall
     if (any_narrow) GA_CHECK(dalloc(stride * (size_t)slots, (void**)&d_ws));
     GA_CHECK(hipMemcpyAsync(d_jobs, jobs.data(), sizeof(Job) * jobs.size(), hipMemcpyHostToDevice, stream));
     GA_CHECK(hipMemcpyAsync(d_off, seq_off, 8 * (size_t)(seq + 1), hipMemcpyHostToDevice, stream));
     GA_CHECK(hipMemcpyAsync(d_chars, chars, (size_t)total_chars, hipMemcpyHostToDevice, stream));
-    GA_CHECK(hipMemsetAsync(d_next, 0, 8 * 3 * (size_t)n_groups, stream));
+    GA_CHECK(hipMemsetAsync(d_next, 0, 8 * 4 * (size_t)n_groups, stream));
     if (timers) { GA_CHECK(hipStreamSynchronize(stream)); lap("alloc + h2d"); }
     int32_t* dbg = nullptr;
     const int64_t dbg_slots = std::max<int64_t>(slots, wide ? (int64_t)prop.multiProcessorCount * 8 : 0);
@@ -1073,20 +1083,23 @@ int align_groups(bool wide, int device, int64_t n_jobs, const int32_t* n_seqs, c
     struct Timed { hipEvent_t a, b; int form; };
     std::vector<Timed> timed;
     auto mark = [&](hipEvent_t* e) { hipError_t r = hipEventCreate(e); if (r == hipSuccess) { events.push_back(*e); r = hipEventRecord(*e, stream); } return r; };
-    auto launch_wide = [&](const Job* host_jobs, size_t nj, const Job* dev_jobs, int32_t* dev_cols, unsigned long long* counter) -> hipError_t {
+    // (form 2, the tall form: the same launch with SharedTall as its fixed block, and no more slots than kTallWorkspace allows)
+    auto launch_wide = [&](int form, const Job* host_jobs, size_t nj, const Job* dev_jobs, int32_t* dev_cols, unsigned long long* counter) -> hipError_t {
+        void (*const kernel)(Params) = form == 2 ? gap_align_kernel<SharedTall> : gap_align_kernel<SharedWide>;
         int wn = 2, wc = 1;
         for (size_t i = 0; i < nj; i++) { wn = std::max(wn, host_jobs[i].n); wc = std::max(wc, std::min<int>(host_jobs[i].max_cols, kWideCols)); }
         auto r16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-        const size_t fixed = r16(sizeof(SharedWide)), rows_b = r16((size_t)wn * (size_t)wc), tb_b = r16(tb_bytes(wc));
+        const size_t fixed = r16(form == 2 ? sizeof(SharedTall) : sizeof(SharedWide)), rows_b = r16((size_t)wn * (size_t)wc), tb_b = r16(tb_bytes(wc));
         bool rows_ws = (place & 2) != 0, tb_ws = (place & 1) != 0;
         if (!rows_ws && fixed + rows_b > kLdsLimit) rows_ws = true;
         if (!tb_ws && fixed + (rows_ws ? 0 : rows_b) + tb_b > kLdsLimit) tb_ws = true;
         const size_t dyn = fixed + (rows_ws ? 0 : rows_b) + (tb_ws ? 0 : tb_b);
-        hipError_t e = hipFuncSetAttribute((const void*)gap_align_kernel<SharedWide>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
+        hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
         if (e != hipSuccess) return e;
         const int wper_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / (dyn + 256)));
-        const int64_t wslots = std::min<int64_t>((int64_t)nj, (int64_t)prop.multiProcessorCount * wper_cu);
         const size_t wstride = slot_bytes(wn, wc, kWideSeq, rows_ws, tb_ws);
+        int64_t wslots = std::min<int64_t>((int64_t)nj, (int64_t)prop.multiProcessorCount * wper_cu);
+        if (form == 2) wslots = std::min<int64_t>(wslots, std::max<int64_t>(1, (int64_t)(kTallWorkspace / wstride)));
         if (wstride * (size_t)wslots > wide_ws_bytes) {
             e = hipStreamSynchronize(stream);      // (an earlier launch may still use the smaller one)
             if (e != hipSuccess) return e;
@@ -1095,12 +1108,13 @@ int align_groups(bool wide, int device, int64_t n_jobs, const int32_t* n_seqs, c
             if (e != hipSuccess) return e;
             wide_ws_bytes = wstride * (size_t)wslots;
         }
-        if (timers) fprintf(stderr, "[gap batch] wide form: %zu jobs, widest %d sequences x %d columns: %zu B of LDS per wavefront (rows in %s, trace-back in %s), %d per CU, %lld slots\n",
-                            nj, wn, wc, dyn, rows_ws ? "the workspace" : "LDS", tb_ws ? "the workspace" : "LDS", wper_cu, (long long)wslots);
+        if (timers) fprintf(stderr, "[gap batch] %s form: %zu jobs, widest %d sequences x %d columns: %zu B of LDS per wavefront (rows in %s, trace-back in %s), %d per CU, %lld slots, %.1f MB of workspace\n",
+                            form == 2 ? "tall" : "wide", nj, wn, wc, dyn, rows_ws ? "the workspace" : "LDS", tb_ws ? "the workspace" : "LDS", wper_cu, (long long)wslots,
+                            (double)(wstride * (size_t)wslots) / 1048576.0);
         Params P{dev_jobs, (int64_t)nj, d_off, d_chars, d_out, dev_cols, counter, d_wide_ws, (int64_t)wstride, wn, wc, rows_ws ? 1 : 0, tb_ws ? 1 : 0, dbg, d_prof};
-        Timed t{nullptr, nullptr, 1};
+        Timed t{nullptr, nullptr, form};
         if (stats && (e = mark(&t.a)) != hipSuccess) return e;
-        hipLaunchKernelGGL(gap_align_kernel<SharedWide>, dim3((unsigned)wslots), dim3(64), dyn, stream, P);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)wslots), dim3(64), dyn, stream, P);
         if ((e = hipGetLastError()) != hipSuccess) return e;
         if (stats) { if ((e = mark(&t.b)) != hipSuccess) return e; timed.push_back(t); }
         return hipSuccess;
@@ -1108,11 +1122,11 @@ int align_groups(bool wide, int device, int64_t n_jobs, const int32_t* n_seqs, c
     std::vector<int32_t> got(jobs.size());
     std::vector<Job> again; std::vector<size_t> again_at; std::vector<int32_t> again_got;
     for (int g = 0; g < n_groups; g++) {
-        const size_t j0 = first[(size_t)g * 2], jw = first[(size_t)g * 2 + 1], j1 = first[(size_t)g * 2 + 2];
+        const size_t j0 = first[(size_t)g * 3], jw = first[(size_t)g * 3 + 1], jt = first[(size_t)g * 3 + 2], j1 = first[(size_t)g * 3 + 3];
         if (j1 > j0) {
             if (jw > j0) {
                 // a group's jobs: their own queue counter, their slice of the job and column arrays; workspace and slots shared
-                Params P{d_jobs + j0, (int64_t)(jw - j0), d_off, d_chars, d_out, d_cols + j0, d_next + 3 * g, d_ws, (int64_t)stride, nmax, cap, 0, 0, dbg, d_prof};
+                Params P{d_jobs + j0, (int64_t)(jw - j0), d_off, d_chars, d_out, d_cols + j0, d_next + 4 * g, d_ws, (int64_t)stride, nmax, cap, 0, 0, dbg, d_prof};
                 const int64_t gslots = std::min<int64_t>((int64_t)(jw - j0), slots);
                 Timed t{nullptr, nullptr, 0};
                 if (stats) GA_CHECK(mark(&t.a));
@@ -1120,7 +1134,8 @@ int align_groups(bool wide, int device, int64_t n_jobs, const int32_t* n_seqs, c
                 GA_CHECK(hipGetLastError());
                 if (stats) { GA_CHECK(mark(&t.b)); timed.push_back(t); }
             }
-            if (j1 > jw) GA_CHECK(launch_wide(jobs.data() + jw, j1 - jw, d_jobs + jw, d_cols + jw, d_next + 3 * g + 1));
+            if (jt > jw) GA_CHECK(launch_wide(1, jobs.data() + jw, jt - jw, d_jobs + jw, d_cols + jw, d_next + 4 * g + 1));
+            if (j1 > jt) GA_CHECK(launch_wide(2, jobs.data() + jt, j1 - jt, d_jobs + jt, d_cols + jt, d_next + 4 * g + 3));
             // the rows of the group: the span of the output its jobs cover (a span may include rows of other groups: the
             // device buffer holds their final bytes if they are done, and they are copied again when they are not)
             int64_t lo = out_bytes, hi = 0;
@@ -1134,7 +1149,7 @@ int align_groups(bool wide, int device, int64_t n_jobs, const int32_t* n_seqs, c
                 if (!again.empty()) {
                     if (!d_again) { GA_CHECK(dalloc(sizeof(Job) * jobs.size(), (void**)&d_again)); GA_CHECK(dalloc(4 * jobs.size(), (void**)&d_again_cols)); }
                     GA_CHECK(hipMemcpyAsync(d_again, again.data(), sizeof(Job) * again.size(), hipMemcpyHostToDevice, stream));
-                    GA_CHECK(launch_wide(again.data(), again.size(), d_again, d_again_cols, d_next + 3 * g + 2));
+                    GA_CHECK(launch_wide(1, again.data(), again.size(), d_again, d_again_cols, d_next + 4 * g + 2));
                     again_got.resize(again.size());
                     GA_CHECK(hipMemcpyAsync(again_got.data(), d_again_cols, 4 * again.size(), hipMemcpyDeviceToHost, stream));
                     GA_CHECK(hipStreamSynchronize(stream));
@@ -1144,12 +1159,13 @@ int align_groups(bool wide, int device, int64_t n_jobs, const int32_t* n_seqs, c
             if (hi > lo) GA_CHECK(hipMemcpyAsync(out_rows + lo, d_out + lo, (size_t)(hi - lo), hipMemcpyDeviceToHost, stream));
             GA_CHECK(hipStreamSynchronize(stream));
             for (size_t i = j0; i < j1; i++) cols[which[i]] = got[i];
-            if (stats) { for (size_t i = j0; i < jw; i++) stats->jobs_narrow += got[i] >= 0; for (size_t i = jw; i < j1; i++) stats->jobs_wide += got[i] >= 0; }
+            if (stats) { for (size_t i = j0; i < jw; i++) stats->jobs_narrow += got[i] >= 0; for (size_t i = jw; i < jt; i++) stats->jobs_wide += got[i] >= 0;
+                         for (size_t i = jt; i < j1; i++) stats->jobs_tall += got[i] >= 0; }
         }
         if (timers) { char what[32]; snprintf(what, sizeof what, "group %d", g + 1); lap(what); }
         if (done) done(ctx, g);
     }
-    for (const Timed& t : timed) { float ms = 0; if (hipEventElapsedTime(&ms, t.a, t.b) == hipSuccess) (t.form ? stats->ms_wide : stats->ms_narrow) += (double)ms; }
+    for (const Timed& t : timed) { float ms = 0; if (hipEventElapsedTime(&ms, t.a, t.b) == hipSuccess) (t.form == 2 ? stats->ms_tall : (t.form ? stats->ms_wide : stats->ms_narrow)) += (double)ms; }
     count_declined();
     if (d_prof) {
         unsigned long long prof[kProfStages];
@@ -1170,7 +1186,7 @@ int align_groups(bool wide, int device, int64_t n_jobs, const int32_t* n_seqs, c
 
 extern "C" int pm_gap_align_batch(int device, int64_t n_jobs, const int32_t* n_seqs, const int64_t* seq_off, const uint8_t* chars,
                                   const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols) {
-    return align_groups(false, device, n_jobs, n_seqs, seq_off, chars, max_cols, row_off, out_rows, out_bytes, cols, 1, &n_jobs, nullptr, nullptr, nullptr);
+    return align_groups(0, device, n_jobs, n_seqs, seq_off, chars, max_cols, row_off, out_rows, out_bytes, cols, 1, &n_jobs, nullptr, nullptr, nullptr);
 }
 // The same batch in groups of consecutive jobs (group g = jobs [group_end[g-1], group_end[g])): everything is uploaded once,
 // the groups are aligned one after the other, and when the rows and column counts of a group are in the caller's memory
@@ -1178,13 +1194,28 @@ extern "C" int pm_gap_align_batch(int device, int64_t n_jobs, const int32_t* n_s
 extern "C" int pm_gap_align_groups(int device, int64_t n_jobs, const int32_t* n_seqs, const int64_t* seq_off, const uint8_t* chars,
                                    const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols,
                                    int n_groups, const int64_t* group_end, void (*done)(void* ctx, int group), void* ctx) {
-    return align_groups(false, device, n_jobs, n_seqs, seq_off, chars, max_cols, row_off, out_rows, out_bytes, cols, n_groups, group_end, done, ctx, nullptr);
+    return align_groups(0, device, n_jobs, n_seqs, seq_off, chars, max_cols, row_off, out_rows, out_bytes, cols, n_groups, group_end, done, ctx, nullptr);
 }
 // ... and with the wide form: the limits of pm_gap_limits(1, ...)
 extern "C" int pm_gap_align_groups_wide(int device, int64_t n_jobs, const int32_t* n_seqs, const int64_t* seq_off, const uint8_t* chars,
                                         const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols,
                                         int n_groups, const int64_t* group_end, void (*done)(void* ctx, int group), void* ctx, pm_gap_stats* stats) {
-    return align_groups(true, device, n_jobs, n_seqs, seq_off, chars, max_cols, row_off, out_rows, out_bytes, cols, n_groups, group_end, done, ctx, stats);
+    pm_gap_tall_stats all;
+    const int rc = align_groups(1, device, n_jobs, n_seqs, seq_off, chars, max_cols, row_off, out_rows, out_bytes, cols, n_groups, group_end, done, ctx, stats ? &all : nullptr);
+    if (stats) *stats = pm_gap_stats{all.jobs_narrow, all.jobs_wide, all.declined, all.ms_narrow, all.ms_wide};
+    return rc;
+}
+// ... and with the tall form: the limits of pm_gap_limits_tall
+extern "C" int pm_gap_align_groups_tall(int device, int64_t n_jobs, const int32_t* n_seqs, const int64_t* seq_off, const uint8_t* chars,
+                                        const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols,
+                                        int n_groups, const int64_t* group_end, void (*done)(void* ctx, int group), void* ctx, pm_gap_tall_stats* stats) {
+    return align_groups(2, device, n_jobs, n_seqs, seq_off, chars, max_cols, row_off, out_rows, out_bytes, cols, n_groups, group_end, done, ctx, stats);
+}
+extern "C" int pm_gap_limits_tall(int* max_seqs, int* max_seq_len, int* max_cols) {
+    if (max_seqs) *max_seqs = kTallSeqs;
+    if (max_seq_len) *max_seq_len = kWideSeq;
+    if (max_cols) *max_cols = kWideCols;
+    return PM_OK;
 }
 extern "C" int pm_gap_limits(int wide, int* max_seqs, int* max_seq_len, int* max_cols) {
     if (max_seqs) *max_seqs = kMaxSeqs;

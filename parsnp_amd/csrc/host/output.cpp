@@ -135,6 +135,11 @@ extern "C" int pm_gap_align_groups_wide(int device, int64_t n_jobs, const int32_
                                         const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols,
                                         int n_groups, const int64_t* group_end, void (*done)(void* ctx, int group), void* ctx, pm_gap_stats* stats) __attribute__((weak));
 extern "C" int pm_gap_limits(int wide, int* max_seqs, int* max_seq_len, int* max_cols) __attribute__((weak));
+// ... and its tall form (alignments of 513 to 2 048 genomes), weak in the same way: without it such a run aligns its gaps on the host
+extern "C" int pm_gap_align_groups_tall(int device, int64_t n_jobs, const int32_t* n_seqs, const int64_t* seq_off, const uint8_t* chars,
+                                        const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols,
+                                        int n_groups, const int64_t* group_end, void (*done)(void* ctx, int group), void* ctx, pm_gap_tall_stats* stats) __attribute__((weak));
+extern "C" int pm_gap_limits_tall(int* max_seqs, int* max_seq_len, int* max_cols) __attribute__((weak));
 namespace parsnp {
 GapCounts gap_counts;
 
@@ -282,12 +287,16 @@ void write_output(Aligner& a, const std::string& stem, bool* gap_note) {
     };
     // The gaps go to the device in ONE batch (pm_gap_align_batch: one wavefront per gap, include/parsnp_mum.h); the few the
     // device does not take -- outside its limits (pm_gap_limits: 320 bases and 640 columns in its wide form, which covers every
-    // gap of the default d = 300), or declined -- are aligned here by the host threads, the widest ones while the device works on
+    // gap of the default d = 300; pm_gap_limits_tall: 2 048 sequences), or declined -- are aligned here by the host threads, the widest ones while the device works on
     // the rest.  PARSNP_HOST_GAPS=1: everything on the host (measurement / tests).
     constexpr unsigned kNarrowCols = 96;                  // a gap with a longer string counts as wide (GapCounts::jobs_wide)
     const bool wide_form = pm_gap_align_groups_wide != nullptr && pm_gap_limits != nullptr;
     int dev_seqs = 512, dev_len = (int)kNarrowCols, dev_cols = (int)kNarrowCols;
     if (wide_form) pm_gap_limits(1, &dev_seqs, &dev_len, &dev_cols);
+    // more genomes than that (every gap has one string per genome): the tall form, where the provider has it -- same batch, same row
+    // capacities, its own entry point; beyond its limit too, the host
+    const bool tall_form = wide_form && n > (size_t)dev_seqs && pm_gap_align_groups_tall != nullptr && pm_gap_limits_tall != nullptr;
+    if (tall_form) pm_gap_limits_tall(&dev_seqs, &dev_len, &dev_cols);
     static const bool host_gaps = test_hook("PARSNP_HOST_GAPS") != nullptr;
     // The LCBs are cut into a few groups of consecutive LCBs with about the same alignment work, one device batch each:
     // the file offsets of a group's records only depend on the groups before it, so its records are written while the
@@ -402,6 +411,7 @@ void write_output(Aligner& a, const std::string& stem, bool* gap_note) {
     const size_t on_device = B.job.size();
     struct Reported { vector<std::promise<int>>* done; size_t n = 0; } reported{&batch_done, 0};
     pm_gap_stats device_stats{0, 0, 0, 0.0, 0.0};
+    pm_gap_tall_stats tall_stats{0, 0, 0, 0, 0.0, 0.0, 0.0};
     std::future<void> device_side = std::async(std::launch::async, [&] {
         int rc = PM_OK;
         if (!B.job.empty()) {
@@ -409,7 +419,10 @@ void write_output(Aligner& a, const std::string& stem, bool* gap_note) {
             for (size_t g = 0; g < ngroups; g++) group_end[g] = (int64_t)batch[g].y1;
             const double t0 = clock_s();
             auto report = [](void* ctx, int) { Reported* r = (Reported*)ctx; (*r->done)[r->n++].set_value(PM_OK); };
-            if (wide_form)
+            if (tall_form)
+                rc = pm_gap_align_groups_tall(-1, (int64_t)B.job.size(), B.nseq.data(), B.seqoff.data(), B.chars.data(), B.maxcols.data(), B.rowoff.data(),
+                                              B.out.data(), (int64_t)B.out.size(), B.cols.data(), (int)ngroups, group_end.data(), report, &reported, &tall_stats);
+            else if (wide_form)
                 rc = pm_gap_align_groups_wide(-1, (int64_t)B.job.size(), B.nseq.data(), B.seqoff.data(), B.chars.data(), B.maxcols.data(), B.rowoff.data(),
                                               B.out.data(), (int64_t)B.out.size(), B.cols.data(), (int)ngroups, group_end.data(), report, &reported, &device_stats);
             else
@@ -799,13 +812,15 @@ void write_output(Aligner& a, const std::string& stem, bool* gap_note) {
         double sum = 0, mx = 0; long arg = 0, on_host = 0;
         for (long x = 0; x < nj; x++) { sum += jt[(size_t)x]; on_host += jobs[(size_t)x].on_host; if (jt[(size_t)x] > mx) { mx = jt[(size_t)x]; arg = x; } }
         gap_counts.host += on_host; gap_counts.host_s += sum;
-        if (device_gaps_failed) device_stats = pm_gap_stats{0, 0, 0, 0.0, 0.0};
+        if (tall_form) device_stats = pm_gap_stats{tall_stats.jobs_narrow, tall_stats.jobs_wide, tall_stats.declined, tall_stats.ms_narrow, tall_stats.ms_wide};
+        if (device_gaps_failed) { device_stats = pm_gap_stats{0, 0, 0, 0.0, 0.0}; tall_stats = pm_gap_tall_stats{0, 0, 0, 0, 0.0, 0.0, 0.0}; }
         else if (!wide_form) device_stats.jobs_narrow = (int64_t)on_device - declined;      // (a provider without the wide form reports nothing)
         gap_counts.device_narrow = (long)device_stats.jobs_narrow; gap_counts.device_wide = (long)device_stats.jobs_wide;
         gap_counts.device_narrow_ms = device_stats.ms_narrow; gap_counts.device_wide_ms = device_stats.ms_wide;
+        gap_counts.device_tall = (long)tall_stats.jobs_tall; gap_counts.device_tall_ms = tall_stats.ms_tall;
         if (dbg && nj)
-            fprintf(stderr, "[output] %ld gap alignments: %zu on the device (%lld narrow form in %.1f ms, %lld wide form in %.1f ms, %ld declined), %.3f s of host work, longest %.3f s (gap of %u columns)\n",
-                    nj, on_device, (long long)device_stats.jobs_narrow, device_stats.ms_narrow, (long long)device_stats.jobs_wide, device_stats.ms_wide, declined, sum, mx, jobs[(size_t)arg].max_len);
+            fprintf(stderr, "[output] %ld gap alignments: %zu on the device (%lld narrow form in %.1f ms, %lld wide form in %.1f ms, %lld tall form in %.1f ms, %ld declined), %.3f s of host work, longest %.3f s (gap of %u columns)\n",
+                    nj, on_device, (long long)device_stats.jobs_narrow, device_stats.ms_narrow, (long long)device_stats.jobs_wide, device_stats.ms_wide, (long long)tall_stats.jobs_tall, tall_stats.ms_tall, declined, sum, mx, jobs[(size_t)arg].max_len);
     }
     if (dbg) {
         long ns = 0, np = 0, nt = 0;

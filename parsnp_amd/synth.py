@@ -267,6 +267,9 @@ CONFIGS = {
     # hypervariable windows: gaps of 97 to about 290 bases between adjacent MUMs, what the default d = 300 gives on real genomes
     "hyper10x300k": ("population", dict(seed=41, n=300_000, n_genomes=10, div=0.01, indel_frac=0.05, windows=dict(count=160))),
     "hyper200x200k": ("population", dict(seed=43, n=200_000, n_genomes=200, div=0.01, indel_frac=0.05, windows=dict(count=100, haplotypes=24))),
+    # more than 512 genomes in ONE alignment: every gap is a job of the device gap aligner's tall form
+    "tall640x100k": ("population", dict(seed=47, n=100_000, n_genomes=640, div=0.02, indel_frac=0.05, windows=dict(count=12, haplotypes=24))),
+    "tall2000x30k": ("population", dict(seed=47, n=30_000, n_genomes=2000, div=0.02, indel_frac=0.05, windows=dict(count=4, haplotypes=24))),
     "poprearr10x400k": ("pop_rearranged", dict(seed=13, n=400_000, n_genomes=10, div=0.05, frac=0.10)),
 }
 
