@@ -49,6 +49,15 @@ class Lib:
         self._check(self.L.pm_gap_limits(C.c_int(1 if wide else 0), C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
 
+    def gap_limits_long(self):
+        """(sequences, bases of a sequence, columns of an alignment) of the device gap aligner's long form: pm_gap_limits_long, the
+        limits of pm_gap_align_groups_long (gaps of a cluster distance d of up to 1 000)"""
+        if not hasattr(self.L, "pm_gap_limits_long"):
+            raise PmError("this provider of the ABI has no pm_gap_limits_long")
+        a, b, c = C.c_int(), C.c_int(), C.c_int()
+        self._check(self.L.pm_gap_limits_long(C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
     def _check(self, rc):
         if rc != 0:
             raise PmError("%s (code %d)" % (self.L.pm_last_error().decode(), rc))

@@ -1,5 +1,5 @@
 // gapalign_hip.hip -- the inter-MUM gap aligner on the MI355X: pm_gap_align_batch, pm_gap_align_groups,
-// pm_gap_align_groups_wide and pm_gap_align_groups_tall (include/parsnp_mum.h).
+// pm_gap_align_groups_wide, pm_gap_align_groups_tall and pm_gap_align_groups_long (include/parsnp_mum.h).
 //
 // Replaces, for a whole run's worth of gaps at once, what the reference's XMFA writer does gap by gap:
 // MuscleInterface::CallMuscleFast (src/MuscleInterface.cpp:37-78, called at src/parsnp.cpp:854-855), i.e. the one
@@ -30,6 +30,9 @@
 // kMaxSeqs = 512 sequences.  The tall form (kTallSeqs = 2 048 sequences with the wide form's columns: one alignment of 2 000 genomes
 // and the reference) is the wide form with its per-sequence arrays four times as long; its rows never fit the LDS, and its slots
 // are bounded by the workspace they need (kTallWorkspace).  The fourth entry point adds it to what the third does.
+// The long form (kLongSeq = 1 024 bases, kLongCols = 2 048 columns, 512 sequences: every gap of a cluster distance d of up to 1 000)
+// is a kernel of its own, one alignment = one WORKGROUP of four wavefronts (align_job_long, below the others); the fifth entry
+// point adds it to what the third does.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -876,6 +879,662 @@ __global__ __launch_bounds__(64) void gap_align_kernel(Params P) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// The long form: one alignment = one WORKGROUP of four wavefronts (kLongThreads), for gaps of up to kLongSeq = 1 024 bases and
+// kLongCols = 2 048 columns (a cluster distance d of up to 1 000).  At that width one wavefront per alignment would take seconds
+// (the DP cells grow with the square), so the stages that are loops over independent items run over all 256 threads, and the
+// pairwise DP -- three quarters of a wide job -- keeps four 64-row stripes of profile A in flight, one per wavefront (nw_long).
+// The arithmetic of every cell and every sum is align_job's, operation by operation; only who computes it differs.
+//   LDS (SharedLong, about 147 KB: one workgroup per CU)   the two profiles, the hand-over rings of the DP, the path and the
+//                                                           column maps, the per-sequence arrays
+//   slot workspace, through flat pointers                   the alignment rows, the trace-back bytes, the six sums of a profile
+//                                                           column before they are gathered, and what every form keeps there
+// Wavefronts wait for each other at workgroup barriers only, every barrier in control flow that all 256 threads take alike: a
+// stage that stays on wavefront 0 (the ordered compactions, the guide tree's merges, the weights, the trace-back, the column
+// maps) is an `if (wave == 0)` without a barrier inside -- its lanes order their own memory traffic with GA_WAVE_SYNC -- and
+// the others wait at the barrier behind it.  A job is given up through S.fail, read by everybody after a barrier.
+constexpr int kLongSeqs = 512, kLongSeq = 1024, kLongCols = 2048;
+constexpr int kLongThreads = 256;
+constexpr int kLongChunk = 64;      // DP steps between two barriers of the sweep
+constexpr int kLongLag = 2;         // chunks a wavefront runs behind the one above it (see nw_long)
+constexpr int kLongRing = 256;      // columns of a hand-over ring (power of two)
+constexpr size_t kLongWorkspace = (size_t)8 << 30;      // bytes of slot workspace a long launch may ask for (a slot of 512 x 2 048 needs 8 MB)
+constexpr size_t kLongAccBytes = (size_t)6 * 4 * kLongCols;
+
+// the lanes of ONE wavefront: their outstanding loads / stores have completed before any of them goes on
+#define GA_WAVE_SYNC() do { __builtin_amdgcn_s_waitcnt(0); __threadfence_block(); __builtin_amdgcn_wave_barrier(); } while (0)
+
+struct __align__(16) SharedLong {
+    static constexpr int kCols = kLongCols, kSeq = kLongSeq, kSeqs = kLongSeqs;
+  union {           // the guide tree is finished (and synchronised on) before the first profile is built
+    struct { float mind[kSeqs]; unsigned nearest[kSeqs]; unsigned node[kSeqs]; float height[kSeqs]; } t;      // tree
+    struct {
+        float fa[4][kCols]; uint8_t orda[kCols]; float opena[kCols], closea[kCols];   // profile A: sorted counts, their letters
+        float sb[4][kCols]; float openb[kCols], closeb[kCols];                           // profile B: scores per letter
+        // the row handed from the stripe of wavefront w to that of wavefront w + 1: a ring (the reader follows kLongLag chunks behind)
+        float rD[3][kLongRing], rM[3][kLongRing], rN[3][kLongRing]; uint8_t rX[3][kLongRing];
+        union {
+            // ... and from wavefront 3 to wavefront 0 of the next four stripes: a whole row (it is read a round later).  The path
+            // and the maps are written after the sweep and dead before the next one
+            struct { float wD[kCols + 2], wM[kCols + 2], wN[kCols + 2]; uint8_t wX[kCols + 2]; };
+            struct { uint8_t path[2 * kCols + 2], rev[2 * kCols + 2]; int16_t mapa[2 * kCols + 2], mapb[2 * kCols + 2]; };
+        };
+        float result[3];
+    } p;
+  };
+    uint8_t letter[256];       // alpha.cpp:125-166 (c_letter, copied)
+    float total_i[kSeqs];      // per internal node: sequential float sum of the weights of its rows, in row order
+    uint16_t ncols_i[kSeqs];   // per internal node: columns of its alignment
+    uint16_t rowlen[kSeqs];    // length of the sequence in row p
+    uint16_t codes[kSeq];
+    uint8_t emit[kSeq];        // a string's 6-mer at p is the first of its kind: its 8-bit multiplicity (0: not emitted)
+    float wrow[kSeqs];         // weight of the sequence in row p
+    int32_t flag;              // a value wavefront 0 (or thread 0) hands to everybody
+    int32_t fail, wild;        // the job is given up / holds a wildcard
+};
+static_assert(sizeof(SharedLong) <= 160 * 1024 - 1024, "the long form's fixed block fits the LDS of a CU");
+static_assert(kLongCols + 2 <= 4096 && (kLongRing & (kLongRing - 1)) == 0, "hand-over masks");
+
+// build_profile over 256 threads: the (sum, column) items are spread over all threads, each sum still runs over the rows in MSA
+// order; the sums wait in the slot's workspace (ACC) until the columns are gathered
+template <bool kWild>
+__device__ void build_profile_long(SharedLong& S, const uint8_t* R, float* ACC, int cap, int lo, int ns, int nc, float total, bool as_a) {
+    const int tid = (int)threadIdx.x;
+    const float f = total != 0 ? 1.0f / total : 1.0f;
+    const bool scale = total != 0;
+    for (int kind = 0; kind < 6; kind++) {
+        const uint32_t cmask = kind < 4 ? (uint32_t)kRowCode : (kind == 4 ? (uint32_t)kRowStart : (uint32_t)kRowEnd);
+        const uint32_t cval = kind < 4 ? (uint32_t)kind : cmask;
+        for (int c = tid; c < nc; c += kLongThreads) {
+            const uint8_t* col = R + (size_t)lo * (size_t)cap + c;
+            float acc = 0;
+            auto fold = [&](uint32_t b, float ws) {
+                if (scale) ws *= f;
+                float add = (b & cmask) == cval ? ws : 0.0f;
+                if (kWild) {
+                    const uint32_t code = b & kRowCode;
+                    if (code >= 4 && code < kRowGap && kind < 4)        // a wildcard: 'X' is half G half A, the others a twentieth of each
+                        add = code == 14 ? ((kind == 2 || kind == 0) ? ws / 2 : 0.0f) : ws / 20;
+                }
+                acc += add;
+            };
+            int s0 = 0;
+            for (; s0 + 8 <= ns; s0 += 8) {
+                uint32_t b[8]; float w[8];
+#pragma unroll
+                for (int k = 0; k < 8; k++) { b[k] = col[(size_t)(s0 + k) * (size_t)cap]; w[k] = S.wrow[lo + s0 + k]; }
+#pragma unroll
+                for (int k = 0; k < 8; k++) fold(b[k], w[k]);
+            }
+            for (; s0 < ns; s0++) fold(col[(size_t)s0 * (size_t)cap], S.wrow[lo + s0]);
+            ACC[kind * kLongCols + c] = acc;
+        }
+    }
+    GA_SYNC();
+    for (int c = tid; c < nc; c += kLongThreads) {
+        float cnt[4] = {ACC[c], ACC[kLongCols + c], ACC[2 * kLongCols + c], ACC[3 * kLongCols + c]};
+        const float start = ACC[4 * kLongCols + c], end = ACC[5 * kLongCols + c];
+        unsigned order[4] = {0, 1, 2, 3};       // profilefrommsa.cpp:180-204: bubble sort, strict <
+        bool any = true;
+        for (int pass = 0; any && pass < 8; pass++) {     // at most 3 passes move anything
+            any = false;
+            for (unsigned k = 0; k < 3; k++) {
+                const unsigned a = order[k], b = order[k + 1];
+                if (cnt[a] < cnt[b]) { order[k + 1] = a; order[k] = b; any = true; }
+            }
+        }
+        const float start_occ = (float)(1.0 - start), end_occ = (float)(1.0 - end);
+        const float open = start_occ * kGapOpen / 2, close = end_occ * kGapOpen / 2;
+        if (as_a) {
+            for (unsigned k = 0; k < 4; k++) S.p.fa[k][c] = cnt[order[k]];
+            S.p.orda[c] = (uint8_t)(order[0] | (order[1] << 2) | (order[2] << 4) | (order[3] << 6));
+            S.p.opena[c] = open; S.p.closea[c] = close;
+        } else {
+            for (unsigned i = 0; i < 4; i++) {
+                float sum = 0;
+                for (unsigned j = 0; j < 4; j++) sum += cnt[j] * c_matrix[i][j];
+                S.p.sb[i][c] = sum;
+            }
+            S.p.openb[c] = open; S.p.closeb[c] = close;
+        }
+    }
+    GA_SYNC();
+}
+
+// nw_small over four wavefronts.  Profile A's rows are cut into 64-row stripes; wavefront w sweeps stripe 4r + w in round r, a lane
+// per row along the anti-diagonals exactly as nw_small does.  A stripe's lane 0 needs, at its step t, what the last lane of the
+// stripe above produced for column t + 1 -- at ITS step t + 63.  Time goes in chunks of kLongChunk = 64 steps with a workgroup
+// barrier after each, and wavefront w runs kLongLag = 2 chunks behind wavefront w - 1: in a chunk it reads columns 64k + 1 ..
+// 64k + 64, which the wavefront above finished in its chunks <= k + 1, i.e. before the last barrier, while that one now writes
+// columns 64k + 66 .. 64k + 130.  So a ring of kLongRing = 256 columns per boundary is enough: a column's place is written again
+// 256 columns later, two barriers after it was read.  The row from wavefront 3 to wavefront 0 is read a round later and is kept
+// whole; within a round wavefront 3 overwrites it six chunks behind wavefront 0's reads.  No wavefront polls memory: a wavefront
+// that has no chunk to do (not started yet, finished, or no rows left in the last round) goes straight to the barrier.
+__device__ bool nw_long(SharedLong& S, uint8_t* TB, int la, int lb, int* plen, bool prof, unsigned long long& prof_sweep, unsigned long long& prof_t0) {
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = uni(tid >> 6);
+    const float e = kGapExtend;
+    const int stride = lb + 1;
+    if (tid == 0) {          // termgaps.cpp:19-33 (TERMGAPS_Half falls through into _Ext): 0, then *= -1
+        S.p.opena[0] = 0.0f * -1.0f; if (la > 1) S.p.closea[la - 1] = 0.0f * -1.0f;
+        S.p.openb[0] = 0.0f * -1.0f; if (lb > 1) S.p.closeb[lb - 1] = 0.0f * -1.0f;
+    }
+    for (int x = tid; x <= la; x += kLongThreads) TB[x * stride] = 0;
+    for (int x = tid; x <= lb; x += kLongThreads) TB[x] = 0;
+    GA_SYNC();
+    const float open_a0 = S.p.opena[0], open_b0 = S.p.openb[0];
+    const float closea0 = S.p.closea[0];
+    // where this wavefront's lane 0 reads the row above its stripe, and where its lane 63 leaves the row below it
+    const float* inD = wave == 0 ? S.p.wD : S.p.rD[wave - 1]; const float* inM = wave == 0 ? S.p.wM : S.p.rM[wave - 1];
+    const float* inN = wave == 0 ? S.p.wN : S.p.rN[wave - 1]; const uint8_t* inX = wave == 0 ? S.p.wX : S.p.rX[wave - 1];
+    float* outD = wave == 3 ? S.p.wD : S.p.rD[wave]; float* outM = wave == 3 ? S.p.wM : S.p.rM[wave];
+    float* outN = wave == 3 ? S.p.wN : S.p.rN[wave]; uint8_t* outX = wave == 3 ? S.p.wX : S.p.rX[wave];
+    const int in_mask = wave == 0 ? 4095 : kLongRing - 1, out_mask = wave == 3 ? 4095 : kLongRing - 1;
+    const int chunks = (64 + lb - 1 + kLongChunk - 1) / kLongChunk;      // of a full stripe: steps 0 .. 64 + lb - 2
+    const int rounds_chunks = chunks + 3 * kLongLag;
+    for (int r0 = 0; r0 < la; r0 += 4 * 64) {
+        const int s0 = r0 + wave * 64;                  // rows above this wavefront's stripe
+        const int i = s0 + lane + 1;                    // this lane's row (1-based)
+        const bool row_ok = i <= la;
+        float fr[4] = {0, 0, 0, 0}, fn[4] = {0, 0, 0, 0}; uint8_t ordr = 0, ordn = 0;
+        float open_a = 0, close_a = 0, close_am2 = 0;
+        if (row_ok) {
+            for (int k = 0; k < 4; k++) fr[k] = S.p.fa[k][i - 1];
+            ordr = S.p.orda[i - 1]; open_a = S.p.opena[i - 1]; close_a = S.p.closea[i - 1];
+            if (i >= 2) close_am2 = S.p.closea[i - 2];
+            if (i < la) { for (int k = 0; k < 4; k++) fn[k] = S.p.fa[k][i]; ordn = S.p.orda[i]; }
+        }
+        const int rows_here = la - s0 < 64 ? la - s0 : 64;      // (<= 0: no stripe for this wavefront in the last round)
+        const int steps = rows_here > 0 ? rows_here + lb - 1 : 0;
+        // outputs of this lane's last two steps
+        float lastM = kMinusInf, lastI = kMinusInf;                         // M[i][j-1]; I[i][j-1]
+        float q1 = 0, q2 = 0; uint8_t x1 = 0, x2 = 0;                     // M[i+1][j+1] produced one / two steps ago
+        float prevD = kMinusInf, prevM = kMinusInf;                       // D[i][j], M[i][j] of the last step (for the lane below)
+        for (int g = 0; g < rounds_chunks; g++) {
+            const int k = g - kLongLag * wave;
+            const int t1 = k < 0 ? 0 : ((k + 1) * kLongChunk < steps ? (k + 1) * kLongChunk : steps);
+            for (int t = k < 0 ? 0 : k * kLongChunk; t < t1; t++) {
+                const int j = t - lane + 1;
+                const bool act = row_ok && j >= 1 && j <= lb;
+                const int jc = j < 1 ? 1 : (j > lb ? lb : j);
+                const float ob = S.p.openb[jc - 1], cb = S.p.closeb[jc - 1], cb2 = S.p.closeb[jc >= 2 ? jc - 2 : 0];
+                const float mc = match_ab(S, fr, ordr, jc - 1);                       // this cell's own match score (column 1 and row 1 start from it)
+                const float mn = match_ab(S, fn, ordn, jc < lb ? jc : lb - 1);        // the match score of the cell below and to the right
+                // what the lane above produced: at its last step (up) and two steps ago (diagonal)
+                float upD = __shfl_up(prevD, 1, 64), upM = __shfl_up(prevM, 1, 64), dgM = __shfl_up(q2, 1, 64);
+                uint8_t dgX = (uint8_t)__shfl_up((int)x2, 1, 64);
+                if (lane == 0 && act) {
+                    if (s0 == 0) { upD = kMinusInf; upM = kMinusInf; }        // row 0: M[0][j] = D[0][j] = -inf for j >= 1
+                    else { upD = inD[j & in_mask]; upM = inM[j & in_mask]; dgM = inN[j & in_mask]; dgX = inX[j & in_mask]; }
+                }
+                q2 = q1; x2 = x1;
+                if (act) {
+                    float m; uint8_t xm;
+                    if (j == 1) {
+                        if (i == la) {
+                            if (la > 1) m = mc + (la - 2) * e + open_a0 + close_am2;
+                            else m = mc + open_a0 + closea0;
+                            xm = kDM;
+                        } else if (i == 1) { m = mc; xm = kMM; }
+                        else { m = mc + open_a0 + (i - 2) * e + close_am2; xm = kDM; }
+                    } else if (i == 1) {
+                        m = mc + open_b0 + (j - 2) * e + cb2; xm = kIM;
+                    } else { m = dgM; xm = dgX; }
+                    // REC_D
+                    const float dd = upD + e, md = upM + open_a;
+                    const bool from_m = !(dd > md);
+                    const float D = from_m ? md : dd;
+                    // REC_I
+                    float iij = j == 1 ? kMinusInf : lastI;
+                    iij += e;
+                    const float mi = (j == 1 ? kMinusInf : lastM) + ob;
+                    const bool open_i = mi >= iij;
+                    const float I = open_i ? mi : iij;
+                    TB[i * stride + j] = (uint8_t)(xm | (from_m ? kMD : 0) | (open_i ? kMI : 0));
+                    if (i < la && j < lb) {
+                        const float dm = D + close_a, im = I + cb, mm = m;
+                        const bool pm = mm >= dm && mm >= im;
+                        const bool pd = !pm && dm >= mm && dm >= im;
+                        float nx = mn;
+                        nx += pm ? mm : (pd ? dm : im);
+                        q1 = nx; x1 = pm ? kMM : (pd ? kDM : kIM);
+                    }
+                    lastM = m; lastI = I; prevD = D; prevM = m;
+                    if (lane == 63 && i < la) {
+                        outD[j & out_mask] = D; outM[j & out_mask] = m;
+                        if (j < lb) { outN[(j + 1) & out_mask] = q1; outX[(j + 1) & out_mask] = x1; }
+                    }
+                    if (i == la && j == lb) { S.p.result[0] = m; S.p.result[1] = D; S.p.result[2] = I; }
+                }
+            }
+            GA_SYNC();
+        }
+    }
+    if (prof) { const unsigned long long t_ = (unsigned long long)clock64(); prof_sweep += t_ - prof_t0; prof_t0 = t_; }
+    // bittraceback.cpp:130-209: one cell after the other, by one lane; the other wavefronts wait at the barrier
+    if (tid == 0) {
+        bool ok = true;
+        const float mab = S.p.result[0], dab = S.p.result[1], iab = S.p.result[2];
+        float score = mab; int type = 0;                  // 0 'M', 1 'D', 2 'I': the codes of the trace-back bits (kMM, kDM, kIM)
+        if (dab > score) { score = dab; type = 1; }
+        if (iab > score) { score = iab; type = 2; }
+        int a = la, b = lb, n = 0;
+        uint8_t* rev = S.p.rev;        // end to start, as the trace-back meets the cells
+        for (;;) {
+            if (n >= 2 * kLongCols + 2) { ok = false; break; }
+            rev[n++] = type == 0 ? (uint8_t)'M' : (type == 1 ? (uint8_t)'D' : (uint8_t)'I');
+            const uint32_t bits = TB[a * stride + b];
+            const uint32_t x = bits & kXM;
+            const int next = type == 0 ? (int)x : (type == 1 ? ((bits & kMD) ? 0 : 1) : ((bits & kMI) ? 0 : 2));
+            const int need_a = type != 2, need_b = type != 1;
+            if ((type == 0 && x == 3) || (need_a && a == 0) || (need_b && b == 0)) { ok = false; break; }
+            a -= need_a; b -= need_b;
+            if (a == 0 && b == 0) break;
+            type = next;
+        }
+        S.flag = ok ? n : -1;
+    }
+    GA_SYNC();
+    const int n = uni(S.flag);
+    for (int x = tid; x < n; x += kLongThreads) S.p.path[x] = S.p.rev[n - 1 - x];
+    GA_SYNC();
+    *plen = n;
+    return n >= 0;
+}
+
+// align_job for a workgroup of kLongThreads threads (the comment above it tells why this is a call, not inlined)
+#if !defined(PM_GAP_INLINE)
+__attribute__((noinline))
+#endif
+__device__ bool align_job_long(SharedLong& S, uint8_t* R, uint8_t* TB, float* ACC, const Slot& W, const Params& P, const Job& job, int* out_cols) {
+    using Sh = SharedLong;
+    constexpr int T = kLongThreads;
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = uni(tid >> 6);
+    const int n = uni(job.n), cap = uni(P.cap);      // (said uniform: every loop with a barrier in it is bounded by such values)
+    unsigned long long prof_acc[kProfStages] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long prof_t0 = (kGapClocks && P.prof) ? (unsigned long long)clock64() : 0;
+    if (n < 2 || n > Sh::kSeqs) return false;
+    if (tid == 0) { S.fail = 0; S.wild = 0; }
+    GA_SYNC();
+    // ---- sequences: lengths, FixAlpha (seq.cpp:331-344) happens when the rows are filled
+    for (int i = tid; i < n; i += T) {
+        const int64_t a = P.seq_off[job.first_seq + i], b = P.seq_off[job.first_seq + i + 1];
+        const int L = (int)(b - a);
+        W.len[i] = L;
+        int bad = 0, wild = 0;
+        if (L <= 0 || L > cap || L > Sh::kSeq) bad = 1;
+        uint64_t h = 1469598103934665603ull;
+        for (int x = 0; x < L; x++) {
+            uint8_t ch = P.chars[a + x];
+            if (S.letter[ch] >= 16) ch = 'N';
+            else if (ch >= 'a' || ch == 'U') bad = 1;
+            if (S.letter[ch] >= 4) wild = 1;
+            h = (h ^ ch) * 1099511628211ull;
+        }
+        W.hash[i] = h ^ (uint64_t)L;
+        if (bad) S.fail = 1;
+        if (wild) S.wild = 1;
+    }
+    GA_SYNC();
+    if (uni(S.fail)) return false;
+    const bool any_wild = uni(S.wild) != 0;
+    auto seq_char = [&](int i, int x) -> uint8_t { uint8_t ch = P.chars[P.seq_off[job.first_seq + i] + x]; return S.letter[ch] >= 16 ? (uint8_t)'N' : ch; };
+
+    GA_STAGE(1); GA_CLOCK(0);
+    // ---- distinct strings: cls[i] = first sequence spelling the same string
+    for (int i = tid; i < n; i += T) {
+        int rep = i;
+        const uint64_t h = W.hash[i]; const int L = W.len[i];
+        for (int o = 0; o < i; o++) {
+            if (W.hash[o] != h || W.len[o] != L) continue;
+            bool same = true;
+            for (int x = 0; x < L && same; x++) same = seq_char(o, x) == seq_char(i, x);
+            if (same) { rep = o; break; }
+        }
+        W.cls[i] = rep;
+    }
+    GA_SYNC();
+    GA_CLOCK(1);
+    if (wave == 0) {            // the representatives in order: ballots of one wavefront
+        int cnt = 0;
+        for (int i0 = 0; i0 < n; i0 += 64) {
+            const int i = i0 + lane;
+            const bool is_rep = i < n && W.cls[i] == i;
+            const unsigned long long m = __ballot(is_rep);
+            if (is_rep) { const int r = cnt + __popcll(m & ((1ull << lane) - 1)); W.repidx[i] = r; W.replist[r] = i; }
+            cnt += __popcll(m);
+        }
+        if (lane == 0) S.flag = cnt;
+    }
+    GA_SYNC();
+    const int u = uni(S.flag);
+    GA_STAGE(2); GA_CLOCK(14);
+    // ---- per distinct string: its distinct 6-mers with 8-bit (wrapping) multiplicities (fastdistnuc.cpp:82-90)
+    for (int a = 0; a < u; a++) {
+        const int i = uni(W.replist[a]), L = uni(W.len[i]);
+        if (L >= 6) {
+            for (int p = tid; p < L; p += T) {
+                uint32_t t = 0;
+                if (p >= 5) for (int x = p - 5; x <= p; x++) { uint8_t l = S.letter[seq_char(i, x)]; if (l >= 4) l = 4; t = t * 6 + l; }
+                S.codes[p] = (uint16_t)t;
+            }
+            GA_SYNC();
+            for (int p = tid; p < L; p += T) {      // counted by all threads ...
+                uint8_t em = 0;
+                if (p >= 5) {
+                    const uint16_t mine = S.codes[p];
+                    bool first = true; int cnt = 0;
+                    for (int q = 5; q < L; q++) { if (S.codes[q] == mine) { cnt++; if (q < p) first = false; } }
+                    if (first) em = (uint8_t)(cnt & 255);
+                }
+                S.emit[p] = em;
+            }
+            GA_SYNC();
+            GA_CLOCK(2);
+            if (wave == 0) {                        // ... and listed in the order of their first positions by wavefront 0
+                int nt = 0;
+                for (int p0 = 0; p0 < L; p0 += 64) {
+                    const int p = p0 + lane;
+                    const uint8_t em = p < L ? S.emit[p] : (uint8_t)0;
+                    const unsigned long long m = __ballot(em != 0);
+                    if (em != 0) {
+                        const int at = nt + __popcll(m & ((1ull << lane) - 1));
+                        W.tcode[(size_t)a * Sh::kSeq + at] = S.codes[p]; W.tcnt[(size_t)a * Sh::kSeq + at] = em;
+                    }
+                    nt += __popcll(m);
+                }
+                if (lane == 0) W.ntup[a] = nt;
+            }
+            GA_SYNC();
+            GA_CLOCK(14);
+        } else if (tid == 0) W.ntup[a] = 0;
+    }
+    GA_SYNC();
+    for (int a = 0; a < u; a++) {
+        const int na = uni(W.ntup[a]);
+        for (int t = tid; t < na; t += T) W.table[W.tcode[(size_t)a * Sh::kSeq + t]] = W.tcnt[(size_t)a * Sh::kSeq + t];
+        GA_SYNC();
+        for (int b = wave; b <= a; b += T / 64) {      // a partner string per wavefront
+            const int nb = uni(W.ntup[b]);
+            int sum = 0;
+            for (int t = lane; t < nb; t += 64) {
+                const uint8_t c1 = W.table[W.tcode[(size_t)b * Sh::kSeq + t]], c2 = W.tcnt[(size_t)b * Sh::kSeq + t];
+                sum += c1 < c2 ? c1 : c2;
+            }
+            sum = wave_sum(sum);
+            if (lane == 0) { W.ucommon[(size_t)a * u + b] = (uint16_t)sum; W.ucommon[(size_t)b * u + a] = (uint16_t)sum; }
+        }
+        GA_SYNC();
+        for (int t = tid; t < na; t += T) W.table[W.tcode[(size_t)a * Sh::kSeq + t]] = 0;
+        GA_SYNC();
+    }
+    GA_STAGE(3); GA_CLOCK(2);
+    // ---- distances (fastdistnuc.cpp:236-262)
+    for (int i = 1; i < n; i++) {
+        const int ci = W.repidx[W.cls[i]];
+        double c11 = W.ucommon[(size_t)ci * u + ci];
+        if (c11 == 0) c11 = 1;
+        for (int j = tid; j < i; j += T) {
+            const int cj = W.repidx[W.cls[j]];
+            double c22 = W.ucommon[(size_t)cj * u + cj];
+            if (c22 == 0) c22 = 1;
+            const unsigned c12 = W.ucommon[(size_t)ci * u + cj];
+            const double d1 = 3.0 * (c11 - c12) / c11;
+            const double d2 = 3.0 * (c22 - c12) / c22;
+            W.dist[tri((unsigned)i, (unsigned)j)] = (float)(d1 < d2 ? d1 : d2);
+        }
+    }
+    if (tid == 0) W.dist[(size_t)n * (n - 1) / 2] = 0.0f;
+    GA_SYNC();
+
+    GA_STAGE(4); GA_CLOCK(3);
+    // ---- UPGMB (upgma2.cpp:133-355): 0.1 * average + 0.9 * minimum linkage, stale row minima kept
+    const unsigned un = (unsigned)n;
+    for (unsigned x = tid; x < un; x += T) {
+        float best = kBigDist; unsigned arg = kNone;
+#pragma unroll 8
+        for (unsigned j = 0; j < un; j++) {
+            if (j == x) continue;
+            const float d = W.dist[tri(x, j)];
+            if (d < best) { best = d; arg = j; }
+        }
+        S.t.mind[x] = best; S.t.nearest[x] = arg; S.t.node[x] = x;
+    }
+    GA_SYNC();
+    GA_CLOCK(4);
+    if (wave == 0) {            // the merges: (value, index) arg-min reductions of one wavefront, one merge after the other
+        for (unsigned k = 0; k + 1 < un; k++) {
+            float best = kBigDist; unsigned lmin = kNone;
+            for (unsigned j = lane; j < un; j += 64) {
+                if (S.t.node[j] == kNone) continue;
+                if (S.t.mind[j] < best) { best = S.t.mind[j]; lmin = j; }
+            }
+            wave_argmin(best, lmin);
+            if (lmin == kNone) { S.fail = 1; break; }
+            const unsigned rmin = uni(S.t.nearest[lmin]);
+            if (rmin == kNone || rmin >= un) { S.fail = 1; break; }
+            constexpr int kRounds = Sh::kSeqs / 64;
+            float dl[kRounds], dr[kRounds];
+            const float dlr = W.dist[tri(lmin, rmin)];
+#pragma unroll
+            for (int r = 0; r < kRounds; r++) {
+                const unsigned j = (unsigned)r * 64 + (unsigned)lane;
+                dl[r] = 0; dr[r] = 0;
+                if (j < un && j != lmin && j != rmin && S.t.node[j] != kNone) { dl[r] = W.dist[tri(lmin, j)]; dr[r] = W.dist[tri(rmin, j)]; }
+            }
+            float new_min = kBigDist; unsigned new_nearest = kNone;
+#pragma unroll
+            for (int r = 0; r < kRounds; r++) {
+                const unsigned j = (unsigned)r * 64 + (unsigned)lane;
+                if (j >= un || j == lmin || j == rmin || S.t.node[j] == kNone) continue;
+                const float nd = kSueff * ((dl[r] + dr[r]) / 2) + (1 - kSueff) * (dl[r] < dr[r] ? dl[r] : dr[r]);
+                if (S.t.nearest[j] == rmin) S.t.nearest[j] = lmin;
+                W.dist[tri(lmin, j)] = nd;
+                if (nd < new_min) { new_min = nd; new_nearest = j; }
+            }
+            wave_argmin(new_min, new_nearest);
+            if (lane == 0) {
+                const float h = dlr / 2;
+                const unsigned ul = S.t.node[lmin], ur = S.t.node[rmin];
+                const float hl = ul < un ? 0 : S.t.height[ul - un];
+                const float hr = ur < un ? 0 : S.t.height[ur - un];
+                const unsigned v = un + k;
+                W.left[v] = ul; W.right[v] = ur;
+                W.parent[ul] = v; W.parent[ur] = v;
+                W.to_parent[ul] = (double)(h - hl); W.to_parent[ur] = (double)(h - hr);
+                S.t.height[k] = h;
+                S.t.node[lmin] = v; S.t.nearest[lmin] = new_nearest; S.t.mind[lmin] = new_min; S.t.node[rmin] = kNone;
+            }
+            GA_WAVE_SYNC();
+        }
+    }
+    GA_SYNC();
+    if (uni(S.fail)) return false;
+    const unsigned root = 2 * un - 2, nodes = 2 * un - 1;
+    GA_STAGE(5); GA_CLOCK(5);
+    // ---- ClustalW weights (clwwt.cpp:65-163), by wavefront 0
+    if (wave == 0) {
+        if (lane == 0) {
+            for (unsigned v = 0; v < nodes; v++) W.under[v] = v < un ? 1 : W.under[W.left[v]] + W.under[W.right[v]];
+            W.lo[root] = 0;
+            for (unsigned v = root; v >= un; v--) { W.lo[W.left[v]] = W.lo[v]; W.lo[W.right[v]] = W.lo[v] + (int32_t)W.under[W.left[v]]; }
+            for (unsigned l = 0; l < un; l++) W.perm[W.lo[l]] = (int32_t)l;
+        }
+        GA_WAVE_SYNC();
+        if (n == 2) { if (lane < 2) W.weight[lane] = 0.5f; }
+        else {
+            for (unsigned v = lane; v < nodes; v += 64) W.strength[v] = v == root ? 0.0 : W.to_parent[v] / (double)W.under[v];
+            GA_WAVE_SYNC();
+            int broken = 0;
+            for (unsigned l = lane; l < un; l += 64) {
+                double sum = 0;
+                unsigned steps = 0;
+                for (unsigned v = l; v != root && steps <= nodes; v = W.parent[v], steps++) { if (v >= nodes) { steps = nodes + 1; break; } sum += W.strength[v]; }
+                if (steps > nodes) broken = 1;
+                if (sum < 0.0001) sum = 1.0;
+                W.weight[l] = (float)sum;
+            }
+            if (wave_sum(broken)) S.fail = 1;        // not a tree: cannot happen, and must not spin if it does
+            else {
+                GA_WAVE_SYNC();
+                float total = 0.0;
+                for (unsigned l = 0; l < un; l++) total += W.weight[l];
+                if (total == 0.0) S.fail = 1;
+                else {
+                    GA_WAVE_SYNC();
+                    for (unsigned l = lane; l < un; l += 64) W.weight[l] /= total;
+                }
+            }
+        }
+    }
+    GA_SYNC();
+    if (uni(S.fail)) return false;
+    GA_STAGE(6); GA_CLOCK(6);
+    // ---- leaves: one-row alignments (row p = leaf p of the root alignment's order; a thread per row)
+    for (int p = tid; p < n; p += T) {
+        const int i = W.perm[p], L = W.len[i];
+        uint8_t* row = R + (size_t)p * (size_t)cap;
+        const int64_t a0 = P.seq_off[job.first_seq + i];
+        for (int x = 0; x < L; x++) { const uint8_t l = S.letter[P.chars[a0 + x]]; row[x] = l >= 16 ? (uint8_t)15 : l; }      // FixAlpha (seq.cpp:331-344): anything else is an 'N'
+        S.wrow[p] = W.weight[i]; S.rowlen[p] = (uint16_t)L;
+    }
+    GA_SYNC();
+    GA_STAGE(7); GA_CLOCK(7);
+    // ---- progressive alignment (progressivealign.cpp:16-82), nodes in ascending order as in align_job (every wavefront fetches the
+    // same 64 nodes' inputs and hands them round among its own lanes)
+    for (unsigned v0 = un; v0 < nodes; v0 += 64) {
+      unsigned my_a = 0, my_b = 0; int my_loa = 0, my_nsa = 0, my_lob = 0, my_nsb = 0;
+      if (v0 + (unsigned)lane < nodes) {
+          my_a = W.left[v0 + lane]; my_b = W.right[v0 + lane];
+          my_loa = W.lo[my_a]; my_nsa = (int)W.under[my_a]; my_lob = W.lo[my_b]; my_nsb = (int)W.under[my_b];
+      }
+      const unsigned vend = v0 + 64 < nodes ? v0 + 64 : nodes;
+      for (unsigned v = v0; v < vend; v++) {
+        const int k = (int)(v - v0);
+        const unsigned a = uni((unsigned)__shfl((int)my_a, k, 64)), b = uni((unsigned)__shfl((int)my_b, k, 64));
+        const int loa = uni(__shfl(my_loa, k, 64)), nsa = uni(__shfl(my_nsa, k, 64)), lob = uni(__shfl(my_lob, k, 64)), nsb = uni(__shfl(my_nsb, k, 64));
+        const int la = uni(a < un ? (int)S.rowlen[loa] : (int)S.ncols_i[a - un]);
+        const int lb = uni(b < un ? (int)S.rowlen[lob] : (int)S.ncols_i[b - un]);
+        const float total_a = a < un ? 0.0f + S.wrow[loa] : S.total_i[a - un];
+        const float total_b = b < un ? 0.0f + S.wrow[lob] : S.total_i[b - un];
+        if (la <= 0 || lb <= 0 || la > Sh::kCols || lb > Sh::kCols) return false;
+        if (ga_stage_on(100)) GA_STAGE_DYN(100 + (int)(v - un) * 10);
+        GA_CLOCK(8);
+        if (any_wild) { build_profile_long<true>(S, R, ACC, cap, loa, nsa, la, total_a, true); build_profile_long<true>(S, R, ACC, cap, lob, nsb, lb, total_b, false); }
+        else { build_profile_long<false>(S, R, ACC, cap, loa, nsa, la, total_a, true); build_profile_long<false>(S, R, ACC, cap, lob, nsb, lb, total_b, false); }
+        int plen = 0;
+        if (ga_stage_on(100)) GA_STAGE_DYN(101 + (int)(v - un) * 10); GA_CLOCK(13);
+        if (!nw_long(S, TB, la, lb, &plen, kGapClocks && P.prof != nullptr, prof_acc[9], prof_t0)) return false;
+        if (ga_stage_on(100)) GA_STAGE_DYN(102 + (int)(v - un) * 10); GA_CLOCK(10);
+        if (plen > cap || plen > Sh::kCols) return false;
+        // aligngivenpath.cpp:124-255: a column of A, of B, or of both (counted with the ballots of wavefront 0)
+        if (wave == 0) {
+            int ca = 0, cb = 0;
+            for (int c0 = 0; c0 < plen; c0 += 64) {
+                const int c = c0 + lane;
+                const uint8_t t = c < plen ? S.p.path[c] : (uint8_t)0;
+                const bool in_a = c < plen && t != 'I', in_b = c < plen && t != 'D';
+                const unsigned long long ma = __ballot(in_a), mb = __ballot(in_b), below = (1ull << lane) - 1;
+                if (c < plen) {
+                    S.p.mapa[c] = in_a ? (int16_t)(ca + __popcll(ma & below)) : (int16_t)-1;
+                    S.p.mapb[c] = in_b ? (int16_t)(cb + __popcll(mb & below)) : (int16_t)-1;
+                }
+                ca += __popcll(ma); cb += __popcll(mb);
+            }
+            if (ca != la || cb != lb) S.fail = 1;
+        }
+        GA_SYNC();
+        if (uni(S.fail)) return false;
+        GA_CLOCK(15);
+        // rows re-spelled in place through the column maps, in chunks of 256 columns from the right end to the left (a column's
+        // source lies at or to the left of it), eight rows at a time; then the gap flags from the finished codes of both neighbours
+        {
+            constexpr int kRows = 8;
+            auto respell = [&](int p0, int np, const int16_t* map) {
+                for (int s0 = 0; s0 < np; s0 += kRows) {
+                    for (int c0 = ((plen - 1) / T) * T; c0 >= 0; c0 -= T) {
+                        const int c = c0 + tid;
+                        const int m = c < plen ? (int)map[c] : -1;
+                        uint8_t val[kRows];
+#pragma unroll
+                        for (int k = 0; k < kRows; k++) {
+                            const uint8_t* row = R + (size_t)(p0 + (s0 + k < np ? s0 + k : np - 1)) * (size_t)cap;
+                            val[k] = m >= 0 ? (uint8_t)(row[m] & kRowCode) : kRowGap;
+                        }
+                        GA_SYNC();      // every thread has read before any thread writes
+#pragma unroll
+                        for (int k = 0; k < kRows; k++) {
+                            if (s0 + k >= np || c >= plen) continue;
+                            R[(size_t)(p0 + s0 + k) * (size_t)cap + c] = val[k];
+                        }
+                        GA_SYNC();
+                    }
+                    for (int c = tid; c < plen; c += T) {
+#pragma unroll
+                        for (int k = 0; k < kRows; k++) {
+                            if (s0 + k >= np) continue;
+                            uint8_t* row = R + (size_t)(p0 + s0 + k) * (size_t)cap;
+                            if (!row_gap(row[c])) continue;
+                            const uint8_t l = c > 0 ? row[c - 1] : (uint8_t)0, r = c + 1 < plen ? row[c + 1] : (uint8_t)0;
+                            row[c] = (uint8_t)(kRowGap | (row_gap(l) ? 0 : kRowStart) | (row_gap(r) ? 0 : kRowEnd));
+                        }
+                    }
+                    GA_SYNC();
+                }
+            };
+            if (plen != la) respell(loa, nsa, S.p.mapa);
+            if (plen != lb) respell(lob, nsb, S.p.mapb);
+        }
+        if (tid == 0) {
+            S.ncols_i[v - un] = (uint16_t)plen;
+            float t = total_a;                       // the merged alignment's rows: A's, then B's
+            for (int x = 0; x < nsb; x++) t += S.wrow[lob + x];
+            S.total_i[v - un] = t;
+        }
+        GA_SYNC();
+        GA_CLOCK(11);
+      }
+    }
+    const int nc = uni((int)S.ncols_i[root - un]);
+    if (nc > uni(job.max_cols)) return false;
+    for (int p = 0; p < n; p++) {                     // row after row, the threads over its columns
+        const uint8_t* src = R + (size_t)p * (size_t)cap;
+        uint8_t* dst = P.out_rows + job.row_off + (int64_t)W.perm[p] * job.max_cols;
+        for (int c = tid; c < nc; c += T) dst[c] = row_char(src[c]);
+    }
+    *out_cols = nc;
+    GA_CLOCK(12);
+    if (kGapClocks && P.prof && tid == 0) for (int k = 0; k < kProfStages; k++) if (prof_acc[k]) atomicAdd(&P.prof[k], prof_acc[k]);
+    return true;
+}
+
+// the long form's kernel: a workgroup of four wavefronts per slot; the fixed block (SharedLong) is dynamic LDS, the rows, the
+// trace-back bytes and the profile sums lie in the slot's workspace
+__global__ __launch_bounds__(kLongThreads) void gap_align_long_kernel(Params P) {
+    extern __shared__ __align__(16) uint8_t long_lds[];
+    const Slot W = carve(P.ws + (size_t)blockIdx.x * (size_t)P.ws_stride, P.nmax, P.cap, kLongSeq, true, true);
+    SharedLong& S = *reinterpret_cast<SharedLong*>(long_lds);
+    float* ACC = (float*)(W.tb + ((tb_bytes(P.cap) + 15) & ~(size_t)15));
+    const int lane = (int)threadIdx.x;      // (the markers' name for the thread that writes them)
+    for (int x = (int)threadIdx.x; x < 256; x += kLongThreads) S.letter[x] = c_letter[x];
+    for (int x = (int)threadIdx.x; x < kTable; x += kLongThreads) W.table[x] = 0;
+    GA_SYNC();
+    for (;;) {
+        // the job is fetched by one thread and handed to the others through LDS: all four wavefronts take and leave a job together
+        if (threadIdx.x == 0) S.flag = (int32_t)atomicAdd(P.next, 1ull);
+        GA_SYNC();
+        const int64_t j = uni(S.flag);
+        GA_SYNC();
+        if (j >= P.njobs) break;
+        const Job job = P.jobs[j];
+        if (ga_stage_on(900) && P.dbg && lane == 0) { P.dbg[blockIdx.x * 2] = (int32_t)j; P.dbg[blockIdx.x * 2 + 1] = 0; }
+        int cols = -1;
+        if (!align_job_long(S, W.rows, W.tb, ACC, W, P, job, &cols)) cols = -1;
+        GA_SYNC();
+        if (threadIdx.x == 0) P.out_cols[j] = cols;
+        if (ga_stage_on(900) && P.dbg && lane == 0) P.dbg[blockIdx.x * 2 + 1] = -1;
+    }
+}
+
 __global__ void warmup_kernel(int* p) { if (threadIdx.x == 0) *p = 1; }
 
 // the last error, process wide: the XMFA writer makes the call on a side thread and asks for the message on another.
@@ -933,16 +1592,18 @@ extern "C" int64_t pm_gap_debug_peek(int32_t* out, int64_t cap) {
 }
 
 namespace {
-// One call of any of the four entry points.  level = 0: pm_gap_align_batch / pm_gap_align_groups, the narrow form alone, with the
+// One call of any of the five entry points.  level = 0: pm_gap_align_batch / pm_gap_align_groups, the narrow form alone, with the
 // limits and the launch they have always had.  level = 1: pm_gap_align_groups_wide -- a job with a sequence of more than kMaxCols
 // bases goes to the wide form, and a job the narrow form declined whose rows may be wider than kMaxCols is run again in the wide
 // form before its group is reported.  level = 2: pm_gap_align_groups_tall -- the same, and a job of more than kMaxSeqs sequences
-// goes to the tall form (which has the wide form's columns: nothing it declines would fare better in a second run).
+// goes to the tall form (which has the wide form's columns: nothing it declines would fare better in a second run).  level = 3:
+// pm_gap_align_groups_long -- what level 1 does, and a job with a sequence of more than kWideSeq bases goes to the long form.
+struct FormStats { int64_t jobs_narrow, jobs_wide, jobs_tall, jobs_long, declined; double ms_narrow, ms_wide, ms_tall, ms_long; };
 int align_groups(int level, int device, int64_t n_jobs, const int32_t* n_seqs, const int64_t* seq_off, const uint8_t* chars,
                  const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols,
-                 int n_groups, const int64_t* group_end, void (*done)(void* ctx, int group), void* ctx, pm_gap_tall_stats* stats) {
+                 int n_groups, const int64_t* group_end, void (*done)(void* ctx, int group), void* ctx, FormStats* stats) {
     const bool wide = level >= 1;
-    if (stats) *stats = pm_gap_tall_stats{0, 0, 0, 0, 0.0, 0.0, 0.0};
+    if (stats) *stats = FormStats{0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0};
     if (n_jobs < 0 || (n_jobs > 0 && (!n_seqs || !seq_off || !chars || !max_cols || !row_off || !out_rows || !cols))) return fail(PM_EINVAL, "bad argument");
     if (n_groups < 1 || !group_end || group_end[n_groups - 1] != n_jobs) return fail(PM_EINVAL, "bad job groups");
     for (int g = 0; g < n_groups; g++) if (group_end[g] < (g ? group_end[g - 1] : 0)) return fail(PM_EINVAL, "bad job groups");
@@ -977,13 +1638,13 @@ int align_groups(int level, int device, int64_t n_jobs, const int32_t* n_seqs, c
         }
         GA_CHECK(table_err);
     }
-    // jobs the device takes, per group the narrow ones, then the wide ones, then the tall ones, each longest first (the cost of one
-    // alignment grows with the square of its width)
+    // jobs the device takes, per group the narrow ones, then the wide ones, then the tall ones, then the long ones, each longest first
+    // (the cost of one alignment grows with the square of its width)
     std::vector<Job> jobs; std::vector<int64_t> which; std::vector<int> group_of_job, form_of_job;
     int64_t seq = 0, total_chars = 0;
     int nmax = 2, cap = 1;             // of the narrow form: the widest job of the call
     std::vector<int> widest((size_t)n_jobs, 0);
-    const int seq_limit = wide ? kWideSeq : kMaxCols, seqs_limit = level >= 2 ? kTallSeqs : kMaxSeqs;
+    const int seq_limit = level >= 3 ? kLongSeq : (wide ? kWideSeq : kMaxCols), seqs_limit = level == 2 ? kTallSeqs : kMaxSeqs;
     int grp = 0;
     for (int64_t j = 0; j < n_jobs; j++) {
         while (grp + 1 < n_groups && j >= group_end[grp]) grp++;
@@ -993,7 +1654,7 @@ int align_groups(int level, int device, int64_t n_jobs, const int32_t* n_seqs, c
         for (int i = 0; i < n && ok; i++) { const int64_t L = seq_off[seq + i + 1] - seq_off[seq + i]; if (L <= 0 || L > seq_limit) ok = false; else w = std::max<int>(w, (int)L); }
         if (ok && row_off[j] + (int64_t)n * max_cols[j] > out_bytes) ok = false;
         if (ok) {
-            const int form = n > kMaxSeqs ? 2 : (w > kMaxCols ? 1 : 0);
+            const int form = n > kMaxSeqs ? 2 : (w > kWideSeq ? 3 : (w > kMaxCols ? 1 : 0));
             jobs.push_back(Job{seq, n, max_cols[j], row_off[j]}); which.push_back(j); group_of_job.push_back(grp); form_of_job.push_back(form); widest[(size_t)j] = w;
             if (!form) { nmax = std::max(nmax, n); cap = std::max(cap, std::min<int>(max_cols[j], kMaxCols)); }
         }
@@ -1002,9 +1663,9 @@ int align_groups(int level, int device, int64_t n_jobs, const int32_t* n_seqs, c
     total_chars = seq_off[seq];
     auto count_declined = [&]() { if (stats) { stats->declined = 0; for (int64_t j = 0; j < n_jobs; j++) stats->declined += cols[j] < 0; } };
     if (jobs.empty()) { count_declined(); all_done(0); return PM_OK; }
-    // in the sorted job list: group g = [first[3g], first[3g+3]), its narrow jobs first, its wide jobs from first[3g+1], its tall
-    // jobs from first[3g+2]
-    std::vector<size_t> first((size_t)n_groups * 3 + 1, 0);
+    // in the sorted job list: group g = [first[4g], first[4g+4]), its narrow jobs first, its wide jobs from first[4g+1], its tall
+    // jobs from first[4g+2], its long jobs from first[4g+3]
+    std::vector<size_t> first((size_t)n_groups * 4 + 1, 0);
     {
         std::vector<size_t> order(jobs.size());
         for (size_t i = 0; i < order.size(); i++) order[i] = i;
@@ -1014,8 +1675,8 @@ int align_groups(int level, int device, int64_t n_jobs, const int32_t* n_seqs, c
             return widest[(size_t)which[a]] > widest[(size_t)which[b]];
         });
         std::vector<Job> j2; std::vector<int64_t> w2;
-        for (size_t i : order) { j2.push_back(jobs[i]); w2.push_back(which[i]); first[(size_t)group_of_job[i] * 3 + (size_t)form_of_job[i] + 1]++; }
-        for (size_t k = 0; k < (size_t)n_groups * 3; k++) first[k + 1] += first[k];
+        for (size_t i : order) { j2.push_back(jobs[i]); w2.push_back(which[i]); first[(size_t)group_of_job[i] * 4 + (size_t)form_of_job[i] + 1]++; }
+        for (size_t k = 0; k < (size_t)n_groups * 4; k++) first[k + 1] += first[k];
         jobs.swap(j2); which.swap(w2);
     }
     const bool timers = getenv("PARSNP_DEBUG_TIMERS") != nullptr;
@@ -1027,7 +1688,7 @@ int align_groups(int level, int device, int64_t n_jobs, const int32_t* n_seqs, c
     GA_CHECK(hipGetDeviceProperties(&prop, device));
     GA_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     auto dalloc = [&](size_t bytes, void** p) { hipError_t e = hipMalloc(p, bytes ? bytes : 1); if (e == hipSuccess) owned.push_back(*p); return e; };
-    const bool any_narrow = [&] { for (int g = 0; g < n_groups; g++) if (first[(size_t)g * 3 + 1] > first[(size_t)g * 3]) return true; return false; }();
+    const bool any_narrow = [&] { for (int g = 0; g < n_groups; g++) if (first[(size_t)g * 4 + 1] > first[(size_t)g * 4]) return true; return false; }();
     // ---- the narrow form.  LDS of a workgroup: the fixed block plus the alignment rows of the widest job and the trace-back bytes;
     // as many workgroups per CU as fit in 160 KB
     constexpr size_t kLdsLimit = 160 * 1024 - 1024;
@@ -1040,7 +1701,7 @@ int align_groups(int level, int device, int64_t n_jobs, const int32_t* n_seqs, c
         if (lds > 64 * 1024) GA_CHECK(hipFuncSetAttribute((const void*)gap_align_kernel<Shared>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rows_lds));
         per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / (lds + 256)));
         size_t most = 0;      // narrow jobs of one group (without a wide job in the call: of the call, as the launch has always been sized)
-        for (int g = 0; g < n_groups; g++) most = std::max(most, first[(size_t)g * 3 + 1] - first[(size_t)g * 3]);
+        for (int g = 0; g < n_groups; g++) most = std::max(most, first[(size_t)g * 4 + 1] - first[(size_t)g * 4]);
         slots = std::min<int64_t>(wide ? (int64_t)most : (int64_t)jobs.size(), (int64_t)prop.multiProcessorCount * per_cu);
         stride = slot_bytes(nmax, cap, kMaxCols, false, false);
     }
@@ -1050,12 +1711,12 @@ int align_groups(int level, int device, int64_t n_jobs, const int32_t* n_seqs, c
     GA_CHECK(dalloc((size_t)total_chars, (void**)&d_chars));
     GA_CHECK(dalloc((size_t)out_bytes, (void**)&d_out));
     GA_CHECK(dalloc(4 * jobs.size(), (void**)&d_cols));
-    GA_CHECK(dalloc(8 * 4 * (size_t)n_groups, (void**)&d_next));      // a queue counter per launch: narrow, wide, wide again, tall
+    GA_CHECK(dalloc(8 * 5 * (size_t)n_groups, (void**)&d_next));      // a queue counter per launch: narrow, wide, wide again, tall, long
     if (any_narrow) GA_CHECK(dalloc(stride * (size_t)slots, (void**)&d_ws));
     GA_CHECK(hipMemcpyAsync(d_jobs, jobs.data(), sizeof(Job) * jobs.size(), hipMemcpyHostToDevice, stream));
     GA_CHECK(hipMemcpyAsync(d_off, seq_off, 8 * (size_t)(seq + 1), hipMemcpyHostToDevice, stream));
     GA_CHECK(hipMemcpyAsync(d_chars, chars, (size_t)total_chars, hipMemcpyHostToDevice, stream));
-    GA_CHECK(hipMemsetAsync(d_next, 0, 8 * 4 * (size_t)n_groups, stream));
+    GA_CHECK(hipMemsetAsync(d_next, 0, 8 * 5 * (size_t)n_groups, stream));
     if (timers) { GA_CHECK(hipStreamSynchronize(stream)); lap("alloc + h2d"); }
     int32_t* dbg = nullptr;
     const int64_t dbg_slots = std::max<int64_t>(slots, wide ? (int64_t)prop.multiProcessorCount * 8 : 0);
@@ -1119,14 +1780,42 @@ int align_groups(int level, int device, int64_t n_jobs, const int32_t* n_seqs, c
         if (stats) { if ((e = mark(&t.b)) != hipSuccess) return e; timed.push_back(t); }
         return hipSuccess;
     };
+    // ---- the long form: a workgroup of four wavefronts per slot, one per CU (its fixed block takes most of the LDS); rows, trace-back
+    // bytes and profile sums in the slot's workspace, which also bounds the slots (kLongWorkspace).  Shares the wide launches' workspace.
+    auto launch_long = [&](const Job* host_jobs, size_t nj, const Job* dev_jobs, int32_t* dev_cols, unsigned long long* counter) -> hipError_t {
+        int wn = 2, wc = 1;
+        for (size_t i = 0; i < nj; i++) { wn = std::max(wn, host_jobs[i].n); wc = std::max(wc, std::min<int>(host_jobs[i].max_cols, kLongCols)); }
+        const size_t dyn = (sizeof(SharedLong) + 15) & ~(size_t)15;
+        hipError_t e = hipFuncSetAttribute((const void*)gap_align_long_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
+        if (e != hipSuccess) return e;
+        const size_t wstride = slot_bytes(wn, wc, kLongSeq, true, true) + kLongAccBytes;
+        const int64_t wslots = std::min<int64_t>(std::min<int64_t>((int64_t)nj, (int64_t)prop.multiProcessorCount), std::max<int64_t>(1, (int64_t)(kLongWorkspace / wstride)));
+        if (wstride * (size_t)wslots > wide_ws_bytes) {
+            e = hipStreamSynchronize(stream);      // (an earlier launch may still use the smaller one)
+            if (e != hipSuccess) return e;
+            if (d_wide_ws) { (void)hipFree(d_wide_ws); owned.erase(std::find(owned.begin(), owned.end(), (void*)d_wide_ws)); d_wide_ws = nullptr; wide_ws_bytes = 0; }
+            e = dalloc(wstride * (size_t)wslots, (void**)&d_wide_ws);
+            if (e != hipSuccess) return e;
+            wide_ws_bytes = wstride * (size_t)wslots;
+        }
+        if (timers) fprintf(stderr, "[gap batch] long form: %zu jobs, widest %d sequences x %d columns: %zu B of LDS per workgroup of %d threads (rows, trace-back and profile sums in the workspace), 1 per CU, %lld slots, %.1f MB of workspace\n",
+                            nj, wn, wc, dyn, kLongThreads, (long long)wslots, (double)(wstride * (size_t)wslots) / 1048576.0);
+        Params P{dev_jobs, (int64_t)nj, d_off, d_chars, d_out, dev_cols, counter, d_wide_ws, (int64_t)wstride, wn, wc, 1, 1, dbg, d_prof};
+        Timed t{nullptr, nullptr, 3};
+        if (stats && (e = mark(&t.a)) != hipSuccess) return e;
+        hipLaunchKernelGGL(gap_align_long_kernel, dim3((unsigned)wslots), dim3(kLongThreads), dyn, stream, P);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if (stats) { if ((e = mark(&t.b)) != hipSuccess) return e; timed.push_back(t); }
+        return hipSuccess;
+    };
     std::vector<int32_t> got(jobs.size());
     std::vector<Job> again; std::vector<size_t> again_at; std::vector<int32_t> again_got;
     for (int g = 0; g < n_groups; g++) {
-        const size_t j0 = first[(size_t)g * 3], jw = first[(size_t)g * 3 + 1], jt = first[(size_t)g * 3 + 2], j1 = first[(size_t)g * 3 + 3];
+        const size_t j0 = first[(size_t)g * 4], jw = first[(size_t)g * 4 + 1], jt = first[(size_t)g * 4 + 2], jl = first[(size_t)g * 4 + 3], j1 = first[(size_t)g * 4 + 4];
         if (j1 > j0) {
             if (jw > j0) {
                 // a group's jobs: their own queue counter, their slice of the job and column arrays; workspace and slots shared
-                Params P{d_jobs + j0, (int64_t)(jw - j0), d_off, d_chars, d_out, d_cols + j0, d_next + 4 * g, d_ws, (int64_t)stride, nmax, cap, 0, 0, dbg, d_prof};
+                Params P{d_jobs + j0, (int64_t)(jw - j0), d_off, d_chars, d_out, d_cols + j0, d_next + 5 * g, d_ws, (int64_t)stride, nmax, cap, 0, 0, dbg, d_prof};
                 const int64_t gslots = std::min<int64_t>((int64_t)(jw - j0), slots);
                 Timed t{nullptr, nullptr, 0};
                 if (stats) GA_CHECK(mark(&t.a));
@@ -1134,8 +1823,9 @@ int align_groups(int level, int device, int64_t n_jobs, const int32_t* n_seqs, c
                 GA_CHECK(hipGetLastError());
                 if (stats) { GA_CHECK(mark(&t.b)); timed.push_back(t); }
             }
-            if (jt > jw) GA_CHECK(launch_wide(1, jobs.data() + jw, jt - jw, d_jobs + jw, d_cols + jw, d_next + 4 * g + 1));
-            if (j1 > jt) GA_CHECK(launch_wide(2, jobs.data() + jt, j1 - jt, d_jobs + jt, d_cols + jt, d_next + 4 * g + 3));
+            if (jt > jw) GA_CHECK(launch_wide(1, jobs.data() + jw, jt - jw, d_jobs + jw, d_cols + jw, d_next + 5 * g + 1));
+            if (jl > jt) GA_CHECK(launch_wide(2, jobs.data() + jt, jl - jt, d_jobs + jt, d_cols + jt, d_next + 5 * g + 3));
+            if (j1 > jl) GA_CHECK(launch_long(jobs.data() + jl, j1 - jl, d_jobs + jl, d_cols + jl, d_next + 5 * g + 4));
             // the rows of the group: the span of the output its jobs cover (a span may include rows of other groups: the
             // device buffer holds their final bytes if they are done, and they are copied again when they are not)
             int64_t lo = out_bytes, hi = 0;
@@ -1149,7 +1839,7 @@ int align_groups(int level, int device, int64_t n_jobs, const int32_t* n_seqs, c
                 if (!again.empty()) {
                     if (!d_again) { GA_CHECK(dalloc(sizeof(Job) * jobs.size(), (void**)&d_again)); GA_CHECK(dalloc(4 * jobs.size(), (void**)&d_again_cols)); }
                     GA_CHECK(hipMemcpyAsync(d_again, again.data(), sizeof(Job) * again.size(), hipMemcpyHostToDevice, stream));
-                    GA_CHECK(launch_wide(1, again.data(), again.size(), d_again, d_again_cols, d_next + 4 * g + 2));
+                    GA_CHECK(launch_wide(1, again.data(), again.size(), d_again, d_again_cols, d_next + 5 * g + 2));
                     again_got.resize(again.size());
                     GA_CHECK(hipMemcpyAsync(again_got.data(), d_again_cols, 4 * again.size(), hipMemcpyDeviceToHost, stream));
                     GA_CHECK(hipStreamSynchronize(stream));
@@ -1160,18 +1850,19 @@ int align_groups(int level, int device, int64_t n_jobs, const int32_t* n_seqs, c
             GA_CHECK(hipStreamSynchronize(stream));
             for (size_t i = j0; i < j1; i++) cols[which[i]] = got[i];
             if (stats) { for (size_t i = j0; i < jw; i++) stats->jobs_narrow += got[i] >= 0; for (size_t i = jw; i < jt; i++) stats->jobs_wide += got[i] >= 0;
-                         for (size_t i = jt; i < j1; i++) stats->jobs_tall += got[i] >= 0; }
+                         for (size_t i = jt; i < jl; i++) stats->jobs_tall += got[i] >= 0; for (size_t i = jl; i < j1; i++) stats->jobs_long += got[i] >= 0; }
         }
         if (timers) { char what[32]; snprintf(what, sizeof what, "group %d", g + 1); lap(what); }
         if (done) done(ctx, g);
     }
-    for (const Timed& t : timed) { float ms = 0; if (hipEventElapsedTime(&ms, t.a, t.b) == hipSuccess) (t.form == 2 ? stats->ms_tall : (t.form ? stats->ms_wide : stats->ms_narrow)) += (double)ms; }
+    for (const Timed& t : timed) { float ms = 0; if (hipEventElapsedTime(&ms, t.a, t.b) == hipSuccess) (t.form == 3 ? stats->ms_long : (t.form == 2 ? stats->ms_tall : (t.form ? stats->ms_wide : stats->ms_narrow))) += (double)ms; }
     count_declined();
     if (d_prof) {
         unsigned long long prof[kProfStages];
         GA_CHECK(hipMemcpy(prof, d_prof, sizeof prof, hipMemcpyDeviceToHost));
         static const char* const names[kProfStages] = {"lengths + hashes", "distinct strings", "6-mers + common counts", "distances", "tree: row minima", "tree: merges", "weights",
-                                                       "leaves", "node set-up", "pairwise DP: init + sweep", "DP: trace-back", "path maps + rows + totals", "output", "profiles", "", ""};
+                                                       "leaves", "node set-up", "pairwise DP: init + sweep", "DP: trace-back", "path maps + rows + totals", "output", "profiles",
+                                                       "long form: ordered lists", "long form: column maps"};
         unsigned long long sum = 0;
         for (int k = 0; k < kProfStages; k++) sum += prof[k];
         for (int k = 0; k < kProfStages; k++)
@@ -1200,7 +1891,7 @@ extern "C" int pm_gap_align_groups(int device, int64_t n_jobs, const int32_t* n_
 extern "C" int pm_gap_align_groups_wide(int device, int64_t n_jobs, const int32_t* n_seqs, const int64_t* seq_off, const uint8_t* chars,
                                         const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols,
                                         int n_groups, const int64_t* group_end, void (*done)(void* ctx, int group), void* ctx, pm_gap_stats* stats) {
-    pm_gap_tall_stats all;
+    FormStats all;
     const int rc = align_groups(1, device, n_jobs, n_seqs, seq_off, chars, max_cols, row_off, out_rows, out_bytes, cols, n_groups, group_end, done, ctx, stats ? &all : nullptr);
     if (stats) *stats = pm_gap_stats{all.jobs_narrow, all.jobs_wide, all.declined, all.ms_narrow, all.ms_wide};
     return rc;
@@ -1209,7 +1900,25 @@ extern "C" int pm_gap_align_groups_wide(int device, int64_t n_jobs, const int32_
 extern "C" int pm_gap_align_groups_tall(int device, int64_t n_jobs, const int32_t* n_seqs, const int64_t* seq_off, const uint8_t* chars,
                                         const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols,
                                         int n_groups, const int64_t* group_end, void (*done)(void* ctx, int group), void* ctx, pm_gap_tall_stats* stats) {
-    return align_groups(2, device, n_jobs, n_seqs, seq_off, chars, max_cols, row_off, out_rows, out_bytes, cols, n_groups, group_end, done, ctx, stats);
+    FormStats all;
+    const int rc = align_groups(2, device, n_jobs, n_seqs, seq_off, chars, max_cols, row_off, out_rows, out_bytes, cols, n_groups, group_end, done, ctx, stats ? &all : nullptr);
+    if (stats) *stats = pm_gap_tall_stats{all.jobs_narrow, all.jobs_wide, all.jobs_tall, all.declined, all.ms_narrow, all.ms_wide, all.ms_tall};
+    return rc;
+}
+// ... and with the long form: the limits of pm_gap_limits_long
+extern "C" int pm_gap_align_groups_long(int device, int64_t n_jobs, const int32_t* n_seqs, const int64_t* seq_off, const uint8_t* chars,
+                                        const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols,
+                                        int n_groups, const int64_t* group_end, void (*done)(void* ctx, int group), void* ctx, pm_gap_long_stats* stats) {
+    FormStats all;
+    const int rc = align_groups(3, device, n_jobs, n_seqs, seq_off, chars, max_cols, row_off, out_rows, out_bytes, cols, n_groups, group_end, done, ctx, stats ? &all : nullptr);
+    if (stats) *stats = pm_gap_long_stats{all.jobs_narrow, all.jobs_wide, all.jobs_long, all.declined, all.ms_narrow, all.ms_wide, all.ms_long};
+    return rc;
+}
+extern "C" int pm_gap_limits_long(int* max_seqs, int* max_seq_len, int* max_cols) {
+    if (max_seqs) *max_seqs = kLongSeqs;
+    if (max_seq_len) *max_seq_len = kLongSeq;
+    if (max_cols) *max_cols = kLongCols;
+    return PM_OK;
 }
 extern "C" int pm_gap_limits_tall(int* max_seqs, int* max_seq_len, int* max_cols) {
     if (max_seqs) *max_seqs = kTallSeqs;

@@ -1,7 +1,9 @@
 // output.cpp -- parsnpAligner.xmfa + parsnpAligner.log, the output contract of the reference's
 // Aligner::writeOutput (src/parsnp.cpp:505-1191).  MUM columns are lower case, inter-MUM gap columns upper case.
 // Gaps in which every genome has >= 1 base and some genome has >= 2 go to libMUSCLE in the reference
-// (:790-865, src/MuscleInterface.cpp:37-78); here they go to gapalign.cpp, the restatement of that aligner.  Should it
+// (:790-865, src/MuscleInterface.cpp:37-78); here they go to the device gap aligner (include/parsnp_mum.h: strings of up to 320
+// bases in alignments of up to 2 048 sequences, of up to 1 024 bases -- a cluster distance d of up to 1 000 -- in alignments of
+// up to 512) and, beyond its limits, to gapalign.cpp, the restatement of that aligner.  Should it
 // ever decline an input, the gap is emitted left-justified and '-'-padded and the log carries a note.
 #include <algorithm>
 #include <chrono>
@@ -140,6 +142,11 @@ extern "C" int pm_gap_align_groups_tall(int device, int64_t n_jobs, const int32_
                                         const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols,
                                         int n_groups, const int64_t* group_end, void (*done)(void* ctx, int group), void* ctx, pm_gap_tall_stats* stats) __attribute__((weak));
 extern "C" int pm_gap_limits_tall(int* max_seqs, int* max_seq_len, int* max_cols) __attribute__((weak));
+// ... and its long form (gap strings of 321 to 1 024 bases: a cluster distance d above the default), weak in the same way
+extern "C" int pm_gap_align_groups_long(int device, int64_t n_jobs, const int32_t* n_seqs, const int64_t* seq_off, const uint8_t* chars,
+                                        const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols,
+                                        int n_groups, const int64_t* group_end, void (*done)(void* ctx, int group), void* ctx, pm_gap_long_stats* stats) __attribute__((weak));
+extern "C" int pm_gap_limits_long(int* max_seqs, int* max_seq_len, int* max_cols) __attribute__((weak));
 namespace parsnp {
 GapCounts gap_counts;
 
@@ -287,9 +294,11 @@ void write_output(Aligner& a, const std::string& stem, bool* gap_note) {
     };
     // The gaps go to the device in ONE batch (pm_gap_align_batch: one wavefront per gap, include/parsnp_mum.h); the few the
     // device does not take -- outside its limits (pm_gap_limits: 320 bases and 640 columns in its wide form, which covers every
-    // gap of the default d = 300; pm_gap_limits_tall: 2 048 sequences), or declined -- are aligned here by the host threads, the widest ones while the device works on
-    // the rest.  PARSNP_HOST_GAPS=1: everything on the host (measurement / tests).
+    // gap of the default d = 300; pm_gap_limits_tall: 2 048 sequences; pm_gap_limits_long: 1 024 bases and 2 048 columns for at most
+    // 512 sequences, every gap of a d up to 1 000), or declined -- are aligned here by the host threads, the widest ones while the
+    // device works on the rest.  PARSNP_HOST_GAPS=1: everything on the host (measurement / tests).
     constexpr unsigned kNarrowCols = 96;                  // a gap with a longer string counts as wide (GapCounts::jobs_wide)
+    constexpr unsigned kWideLen = 320;                    // ... and one with a string longer than this as long (GapCounts::jobs_long)
     const bool wide_form = pm_gap_align_groups_wide != nullptr && pm_gap_limits != nullptr;
     int dev_seqs = 512, dev_len = (int)kNarrowCols, dev_cols = (int)kNarrowCols;
     if (wide_form) pm_gap_limits(1, &dev_seqs, &dev_len, &dev_cols);
@@ -297,6 +306,15 @@ void write_output(Aligner& a, const std::string& stem, bool* gap_note) {
     // capacities, its own entry point; beyond its limit too, the host
     const bool tall_form = wide_form && n > (size_t)dev_seqs && pm_gap_align_groups_tall != nullptr && pm_gap_limits_tall != nullptr;
     if (tall_form) pm_gap_limits_tall(&dev_seqs, &dev_len, &dev_cols);
+    // a gap string beyond the wide form's bases (a cluster distance above the default): the long form, where the provider has it and
+    // the alignment has no more sequences than it takes.  A run without such a gap makes the call it has always made.
+    bool long_form = false;
+    if (wide_form && !tall_form && n <= (size_t)dev_seqs && pm_gap_align_groups_long != nullptr && pm_gap_limits_long != nullptr) {
+        for (long x = 0; x < nj && !long_form; x++) long_form = jobs[(size_t)x].max_len > (unsigned)dev_len;
+        int long_seqs = 0;
+        if (long_form) { pm_gap_limits_long(&long_seqs, nullptr, nullptr); long_form = n <= (size_t)long_seqs; }
+        if (long_form) pm_gap_limits_long(&dev_seqs, &dev_len, &dev_cols);
+    }
     static const bool host_gaps = test_hook("PARSNP_HOST_GAPS") != nullptr;
     // The LCBs are cut into a few groups of consecutive LCBs with about the same alignment work, one device batch each:
     // the file offsets of a group's records only depend on the groups before it, so its records are written while the
@@ -323,7 +341,7 @@ void write_output(Aligner& a, const std::string& stem, bool* gap_note) {
     for (size_t g = 0; g < ngroups; g++) for (size_t z = batch[g].z0; z < batch[g].z1; z++) group_of[z] = (int)g;
     for (long x = 0; x < nj; x++) jobs[(size_t)x].grp = group_of[jobs[(size_t)x].z];
     gap_counts.jobs = nj;
-    for (long x = 0; x < nj; x++) { gap_counts.jobs_wide += jobs[(size_t)x].max_len > kNarrowCols; gap_counts.longest = std::max<long>(gap_counts.longest, (long)jobs[(size_t)x].max_len); }
+    for (long x = 0; x < nj; x++) { gap_counts.jobs_wide += jobs[(size_t)x].max_len > kNarrowCols; gap_counts.jobs_long += jobs[(size_t)x].max_len > kWideLen; gap_counts.longest = std::max<long>(gap_counts.longest, (long)jobs[(size_t)x].max_len); }
     if (!host_gaps && n <= (size_t)dev_seqs) {
         int64_t out_bytes = 0;
         for (size_t g = 0; g < ngroups; g++) {               // group after group; the sorted order carries over: every group is longest first
@@ -412,6 +430,7 @@ void write_output(Aligner& a, const std::string& stem, bool* gap_note) {
     struct Reported { vector<std::promise<int>>* done; size_t n = 0; } reported{&batch_done, 0};
     pm_gap_stats device_stats{0, 0, 0, 0.0, 0.0};
     pm_gap_tall_stats tall_stats{0, 0, 0, 0, 0.0, 0.0, 0.0};
+    pm_gap_long_stats long_stats{0, 0, 0, 0, 0.0, 0.0, 0.0};
     std::future<void> device_side = std::async(std::launch::async, [&] {
         int rc = PM_OK;
         if (!B.job.empty()) {
@@ -422,6 +441,9 @@ void write_output(Aligner& a, const std::string& stem, bool* gap_note) {
             if (tall_form)
                 rc = pm_gap_align_groups_tall(-1, (int64_t)B.job.size(), B.nseq.data(), B.seqoff.data(), B.chars.data(), B.maxcols.data(), B.rowoff.data(),
                                               B.out.data(), (int64_t)B.out.size(), B.cols.data(), (int)ngroups, group_end.data(), report, &reported, &tall_stats);
+            else if (long_form)
+                rc = pm_gap_align_groups_long(-1, (int64_t)B.job.size(), B.nseq.data(), B.seqoff.data(), B.chars.data(), B.maxcols.data(), B.rowoff.data(),
+                                              B.out.data(), (int64_t)B.out.size(), B.cols.data(), (int)ngroups, group_end.data(), report, &reported, &long_stats);
             else if (wide_form)
                 rc = pm_gap_align_groups_wide(-1, (int64_t)B.job.size(), B.nseq.data(), B.seqoff.data(), B.chars.data(), B.maxcols.data(), B.rowoff.data(),
                                               B.out.data(), (int64_t)B.out.size(), B.cols.data(), (int)ngroups, group_end.data(), report, &reported, &device_stats);
@@ -492,11 +514,11 @@ void write_output(Aligner& a, const std::string& stem, bool* gap_note) {
             gaps_to_align(a, ct, &aligned);
             const double t0 = clock_s();
             for (auto& tg : aligned) tg.second.failed = !gap_align(tg.second.seq, &tg.second.aligned);
-            long wide_here = 0, longest_here = 0;
-            for (auto& tg : aligned) { wide_here += tg.second.max_len > kNarrowCols; longest_here = std::max<long>(longest_here, (long)tg.second.max_len); }
+            long wide_here = 0, long_here = 0, longest_here = 0;
+            for (auto& tg : aligned) { wide_here += tg.second.max_len > kNarrowCols; long_here += tg.second.max_len > kWideLen; longest_here = std::max<long>(longest_here, (long)tg.second.max_len); }
             const double spent = clock_s() - t0;
 #pragma omp critical(parsnp_gap_counts)
-            { gap_counts.jobs += (long)aligned.size(); gap_counts.host += (long)aligned.size(); gap_counts.jobs_wide += wide_here;
+            { gap_counts.jobs += (long)aligned.size(); gap_counts.host += (long)aligned.size(); gap_counts.jobs_wide += wide_here; gap_counts.jobs_long += long_here;
               gap_counts.longest = std::max(gap_counts.longest, longest_here); gap_counts.host_s += spent; }
         } else {
             for (size_t t = 0; t < pl.gjob.size(); t++) {
@@ -813,14 +835,16 @@ void write_output(Aligner& a, const std::string& stem, bool* gap_note) {
         for (long x = 0; x < nj; x++) { sum += jt[(size_t)x]; on_host += jobs[(size_t)x].on_host; if (jt[(size_t)x] > mx) { mx = jt[(size_t)x]; arg = x; } }
         gap_counts.host += on_host; gap_counts.host_s += sum;
         if (tall_form) device_stats = pm_gap_stats{tall_stats.jobs_narrow, tall_stats.jobs_wide, tall_stats.declined, tall_stats.ms_narrow, tall_stats.ms_wide};
-        if (device_gaps_failed) { device_stats = pm_gap_stats{0, 0, 0, 0.0, 0.0}; tall_stats = pm_gap_tall_stats{0, 0, 0, 0, 0.0, 0.0, 0.0}; }
+        if (long_form) device_stats = pm_gap_stats{long_stats.jobs_narrow, long_stats.jobs_wide, long_stats.declined, long_stats.ms_narrow, long_stats.ms_wide};
+        if (device_gaps_failed) { device_stats = pm_gap_stats{0, 0, 0, 0.0, 0.0}; tall_stats = pm_gap_tall_stats{0, 0, 0, 0, 0.0, 0.0, 0.0}; long_stats = pm_gap_long_stats{0, 0, 0, 0, 0.0, 0.0, 0.0}; }
         else if (!wide_form) device_stats.jobs_narrow = (int64_t)on_device - declined;      // (a provider without the wide form reports nothing)
         gap_counts.device_narrow = (long)device_stats.jobs_narrow; gap_counts.device_wide = (long)device_stats.jobs_wide;
         gap_counts.device_narrow_ms = device_stats.ms_narrow; gap_counts.device_wide_ms = device_stats.ms_wide;
         gap_counts.device_tall = (long)tall_stats.jobs_tall; gap_counts.device_tall_ms = tall_stats.ms_tall;
+        gap_counts.device_long = (long)long_stats.jobs_long; gap_counts.device_long_ms = long_stats.ms_long;
         if (dbg && nj)
-            fprintf(stderr, "[output] %ld gap alignments: %zu on the device (%lld narrow form in %.1f ms, %lld wide form in %.1f ms, %lld tall form in %.1f ms, %ld declined), %.3f s of host work, longest %.3f s (gap of %u columns)\n",
-                    nj, on_device, (long long)device_stats.jobs_narrow, device_stats.ms_narrow, (long long)device_stats.jobs_wide, device_stats.ms_wide, (long long)tall_stats.jobs_tall, tall_stats.ms_tall, declined, sum, mx, jobs[(size_t)arg].max_len);
+            fprintf(stderr, "[output] %ld gap alignments: %zu on the device (%lld narrow form in %.1f ms, %lld wide form in %.1f ms, %lld tall form in %.1f ms, %lld long form in %.1f ms, %ld declined), %.3f s of host work, longest %.3f s (gap of %u columns)\n",
+                    nj, on_device, (long long)device_stats.jobs_narrow, device_stats.ms_narrow, (long long)device_stats.jobs_wide, device_stats.ms_wide, (long long)tall_stats.jobs_tall, tall_stats.ms_tall, (long long)long_stats.jobs_long, long_stats.ms_long, declined, sum, mx, jobs[(size_t)arg].max_len);
     }
     if (dbg) {
         long ns = 0, np = 0, nt = 0;

@@ -270,6 +270,10 @@ CONFIGS = {
     # more than 512 genomes in ONE alignment: every gap is a job of the device gap aligner's tall form
     "tall640x100k": ("population", dict(seed=47, n=100_000, n_genomes=640, div=0.02, indel_frac=0.05, windows=dict(count=12, haplotypes=24))),
     "tall2000x30k": ("population", dict(seed=47, n=30_000, n_genomes=2000, div=0.02, indel_frac=0.05, windows=dict(count=4, haplotypes=24))),
+    # windows of 330 to 900 bases, to be run with a cluster distance d = 1000: gaps of more than 320 bases between adjacent MUMs, the
+    # jobs of the device gap aligner's long form (at the default d = 300 such a window ends the cluster instead)
+    "long10x300k": ("population", dict(seed=51, n=300_000, n_genomes=10, div=0.01, indel_frac=0.05, windows=dict(count=60, min_len=330, max_len=900))),
+    "long200x150k": ("population", dict(seed=53, n=150_000, n_genomes=200, div=0.01, indel_frac=0.05, windows=dict(count=30, haplotypes=24, min_len=330, max_len=900))),
     "poprearr10x400k": ("pop_rearranged", dict(seed=13, n=400_000, n_genomes=10, div=0.05, frac=0.10)),
 }
 
