@@ -47,7 +47,14 @@ struct HostBackend {
                     launch("pack", (lens[g] + 31) / 32, pm::PackStrand{seqs[g], lens[g], s, blk, goff[2 * (size_t)g + (size_t)s] / 32});
         return true;
     }
-    template <class F> void launch_wave(const char*, int64_t n, F f) { for (int64_t i = 0; i < n; i++) f.wave(i); }
+    // PM_EMU_REVERSE_WAVES=<launch name>: that launch runs its wavefronts last to first.  The wavefronts of a launch do not depend on one
+    // another, so the result must be the same; a kernel whose wavefronts share memory words (the first and last word of a
+    // StoreMarkOrdered walk) shows a lost update only when a LATER wavefront has written first, which on the device is a matter of timing
+    template <class F> void launch_wave(const char* name, int64_t n, F f) {
+        const char* rev = getenv("PM_EMU_REVERSE_WAVES");
+        if (rev && name && !strcmp(rev, name)) { for (int64_t i = n - 1; i >= 0; i--) f.wave(i); return; }
+        for (int64_t i = 0; i < n; i++) f.wave(i);
+    }
     void exclusive_scan(const int64_t* in, int64_t* out, size_t n) { int64_t a = 0; for (size_t i = 0; i < n; i++) { int64_t v = in[i]; out[i] = a; a += v; } }
     void sort_pairs(uint64_t* ki, uint64_t* ko, uint64_t* vi, uint64_t* vo, size_t n, int) {
         std::vector<size_t> idx(n);
