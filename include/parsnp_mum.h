@@ -337,9 +337,10 @@ int pm_gap_align_batch(int device, int64_t n_jobs, const int32_t* n_seqs, const 
  * counts of group g are in the caller's arrays `done(ctx, g)` is called from the calling thread -- the caller may use them
  * while the later groups are still being aligned (the XMFA writer lays out and writes the records of the LCBs whose gaps
  * are done).  On an error return the groups after the last one reported have not been reported.  done may be NULL.
- * The rows of a group come back in ONE copy of the span of out_rows that its accepted jobs cover: the row areas of the
- * groups must not interleave (row_off ascending with the job number, as the batch form lays them out), and the rows of a
- * declined job (cols[j] = -1) that lie inside such a span hold unspecified bytes afterwards.
+ * The rows of a group come back as the row areas of its aligned jobs, neighbouring areas in one copy (a group without a
+ * declined job, laid out job after job as the batch form lays them out, is ONE copy).  Only those areas are written: the
+ * row area of a declined job (cols[j] = -1) and everything outside the row areas keep the caller's bytes; inside the area
+ * of an aligned job the bytes behind column cols[j] of a row are unspecified.
  * pm_gap_last_error(): the message of the last failed call of this process, from any thread. */
 int pm_gap_align_groups(int device, int64_t n_jobs, const int32_t* n_seqs, const int64_t* seq_off, const uint8_t* chars,
                         const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols,

@@ -1810,6 +1810,7 @@ int align_groups(int level, int device, int64_t n_jobs, const int32_t* n_seqs, c
     };
     std::vector<int32_t> got(jobs.size());
     std::vector<Job> again; std::vector<size_t> again_at; std::vector<int32_t> again_got;
+    std::vector<std::pair<int64_t, int64_t>> spans;
     for (int g = 0; g < n_groups; g++) {
         const size_t j0 = first[(size_t)g * 4], jw = first[(size_t)g * 4 + 1], jt = first[(size_t)g * 4 + 2], jl = first[(size_t)g * 4 + 3], j1 = first[(size_t)g * 4 + 4];
         if (j1 > j0) {
@@ -1826,11 +1827,8 @@ int align_groups(int level, int device, int64_t n_jobs, const int32_t* n_seqs, c
             if (jt > jw) GA_CHECK(launch_wide(1, jobs.data() + jw, jt - jw, d_jobs + jw, d_cols + jw, d_next + 5 * g + 1));
             if (jl > jt) GA_CHECK(launch_wide(2, jobs.data() + jt, jl - jt, d_jobs + jt, d_cols + jt, d_next + 5 * g + 3));
             if (j1 > jl) GA_CHECK(launch_long(jobs.data() + jl, j1 - jl, d_jobs + jl, d_cols + jl, d_next + 5 * g + 4));
-            // the rows of the group: the span of the output its jobs cover (a span may include rows of other groups: the
-            // device buffer holds their final bytes if they are done, and they are copied again when they are not)
-            int64_t lo = out_bytes, hi = 0;
-            for (size_t i = j0; i < j1; i++) { lo = std::min(lo, jobs[i].row_off); hi = std::max(hi, jobs[i].row_off + (int64_t)jobs[i].n * jobs[i].max_cols); }
             GA_CHECK(hipMemcpyAsync(got.data() + j0, d_cols + j0, 4 * (j1 - j0), hipMemcpyDeviceToHost, stream));
+            if (!wide) GA_CHECK(hipStreamSynchronize(stream));
             if (wide) {
                 // what the narrow form declined although its rows may be wider than the narrow form's columns: once more, wide
                 GA_CHECK(hipStreamSynchronize(stream));
@@ -1846,7 +1844,19 @@ int align_groups(int level, int device, int64_t n_jobs, const int32_t* n_seqs, c
                     for (size_t k = 0; k < again.size(); k++) { got[again_at[k]] = again_got[k]; if (stats && again_got[k] >= 0) { stats->jobs_wide++; stats->jobs_narrow--; } }
                 }
             }
-            if (hi > lo) GA_CHECK(hipMemcpyAsync(out_rows + lo, d_out + lo, (size_t)(hi - lo), hipMemcpyDeviceToHost, stream));
+            // the rows of the group: the areas of its ALIGNED jobs, neighbours in one copy (one copy for a group without a declined
+            // job, laid out job after job).  The area of a declined job keeps the caller's bytes: the device buffer behind it was
+            // never written, or holds an alignment that was given up half-way
+            spans.clear();
+            for (size_t i = j0; i < j1; i++) if (got[i] >= 0) spans.emplace_back(jobs[i].row_off, jobs[i].row_off + (int64_t)jobs[i].n * jobs[i].max_cols);
+            std::sort(spans.begin(), spans.end());
+            for (size_t a = 0; a < spans.size();) {
+                int64_t lo = spans[a].first, hi = spans[a].second;
+                size_t b = a + 1;
+                while (b < spans.size() && spans[b].first <= hi) { hi = std::max(hi, spans[b].second); b++; }
+                if (hi > lo) GA_CHECK(hipMemcpyAsync(out_rows + lo, d_out + lo, (size_t)(hi - lo), hipMemcpyDeviceToHost, stream));
+                a = b;
+            }
             GA_CHECK(hipStreamSynchronize(stream));
             for (size_t i = j0; i < j1; i++) cols[which[i]] = got[i];
             if (stats) { for (size_t i = j0; i < jw; i++) stats->jobs_narrow += got[i] >= 0; for (size_t i = jw; i < jt; i++) stats->jobs_wide += got[i] >= 0;

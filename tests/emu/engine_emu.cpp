@@ -73,7 +73,8 @@ static const char* pm_backend_name = "emu";
 static PmBackend* pm_backend_open(int, std::string*) { return new HostBackend; }
 #include "../../parsnp_amd/csrc/engine/abi_glue.h"
 
-// the device gap aligner is a HIP kernel with no host emulation: decline every job, the host aligner takes them
+// THIS library does not execute the device gap aligner: decline every job, the host aligner takes them.  (Its long form runs on the
+// host in tests/emu/gap_emu.cpp, a library of its own that takes long jobs only; its one-wavefront forms run on the device alone.)
 extern "C" int pm_gap_align_batch(int, int64_t n_jobs, const int32_t*, const int64_t*, const uint8_t*, const int32_t*, const int64_t*, uint8_t*, int64_t, int32_t* cols) {
     for (int64_t j = 0; j < n_jobs; j++) cols[j] = -1;
     return PM_OK;

@@ -119,9 +119,16 @@ def test_fresh_sets_against_reference(device):
     blks = [b for b in gapgen.blocks(31, 300, lengths=(1, 2, 3, 5, 7, 10, 15, 30, 60, 120)) if fits(b)]
     wants = gapgen.reference_align(blks)
     got = device(blks)
+    declined = 0
     for blk, want, rows in zip(blks, wants, got):
-        if rows is not None:
+        assert len({len(r) for r in want}) == 1 and [r.replace("-", "") for r in want] == blk      # the reference aligned it
+        # declined exactly when the alignment is wider than the row capacity the test gave it (every block fits the other limits)
+        if len(want[0]) > min(DEVICE_COLS, (max(len(s) for s in blk) * 3) // 2 + 16):
+            assert rows is None, blk
+            declined += 1
+        else:
             assert rows == want, blk
+    assert len(blks) - declined > 250
 
 
 def test_groups_report_in_order_and_match_the_batch(device):
