@@ -399,8 +399,9 @@ int pm_gap_limits_tall(int* max_seqs, int* max_seq_len, int* max_cols);
  * one workgroup of four wavefronts per alignment, four 64-row stripes of the pairwise DP in flight at once, its rows and
  * trace-back bytes in the device workspace; per group the long jobs are launched after the wide ones, longest first, with a
  * queue of their own, on one slot per compute unit (as far as 8 GiB of workspace allow: a slot of 512 x 2 048 needs 8 MB).
- * More than 512 sequences COMBINED with a sequence of more than 320 bases is outside every form: such a job stays with the
- * caller's host path (pm_gap_align_groups_tall takes more sequences, this entry point longer ones, neither both).
+ * More than 512 sequences COMBINED with a sequence of more than 320 bases is outside this entry point and the one above
+ * (pm_gap_align_groups_tall takes more sequences, this entry point longer ones, neither both): pm_gap_align_groups_long_tall below
+ * takes such a job.
  *   cols[j] = -1   only: fewer than 2 or more than 512 sequences, a sequence that is empty or longer than 1 024 bases, an
  *                  intermediate alignment wider than 2 048 columns or than max_cols[j], a lower-case letter or a 'U', or a case
  *                  in which MUSCLE itself quits.  No job is declined for the LDS it would need.
@@ -415,6 +416,29 @@ int pm_gap_align_groups_long(int device, int64_t n_jobs, const int32_t* n_seqs, 
                              int n_groups, const int64_t* group_end, void (*done)(void* ctx, int group), void* ctx, pm_gap_long_stats* stats);
 /* The limits of pm_gap_align_groups_long (512 sequences, 1 024 bases, 2 048 columns).  Any pointer may be NULL.  Needs no device. */
 int pm_gap_limits_long(int* max_seqs, int* max_seq_len, int* max_cols);
+/* The same call with the device's long-tall form beside the other four: the whole rectangle of 2 048 sequences x 1 024 bases,
+ * what an alignment of more than 511 query genomes run with a raised cluster distance produces.  The five entry points above keep
+ * their limits exactly; this one takes every job within pm_gap_limits_long_tall: up to 2 048 sequences of up to 1 024 bases each
+ * whose intermediate alignments stay within 2 048 columns.  A job of at most 512 sequences runs exactly as in
+ * pm_gap_align_groups_long (narrow, wide or long form, the second run included); a job of 513 to 2 048 sequences with no sequence
+ * longer than 320 bases runs in the tall form exactly as in pm_gap_align_groups_tall; a job of 513 to 2 048 sequences with a
+ * longer sequence runs in the long-tall form -- the long form's kernel with its per-sequence arrays four times as long and the
+ * per-node weight totals in the device workspace; per group the long-tall jobs are launched after the long ones, longest first,
+ * with a queue of their own, on one slot per compute unit (as far as 8 GiB of workspace allow: a slot of 2 048 x 2 048 needs 31 MB).
+ *   cols[j] = -1   only: fewer than 2 or more than 2 048 sequences, a sequence that is empty or longer than 1 024 bases, an
+ *                  intermediate alignment wider than 2 048 columns or than max_cols[j], a lower-case letter or a 'U', or a case
+ *                  in which MUSCLE itself quits.  No job is declined for the LDS it would need.
+ * stats (may be NULL): what the call did; a record of its own, the older ones keep their size. */
+typedef struct pm_gap_long_tall_stats {
+    int64_t jobs_narrow, jobs_wide, jobs_tall, jobs_long, jobs_long_tall;   /* jobs aligned by each form */
+    int64_t declined;                                                       /* jobs answered with cols = -1 */
+    double ms_narrow, ms_wide, ms_tall, ms_long, ms_long_tall;              /* kernel time of each form, summed over the launches (HIP events) */
+} pm_gap_long_tall_stats;
+int pm_gap_align_groups_long_tall(int device, int64_t n_jobs, const int32_t* n_seqs, const int64_t* seq_off, const uint8_t* chars,
+                                  const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols,
+                                  int n_groups, const int64_t* group_end, void (*done)(void* ctx, int group), void* ctx, pm_gap_long_tall_stats* stats);
+/* The limits of pm_gap_align_groups_long_tall (2 048 sequences, 1 024 bases, 2 048 columns).  Any pointer may be NULL.  Needs no device. */
+int pm_gap_limits_long_tall(int* max_seqs, int* max_seq_len, int* max_cols);
 
 /* Device-side timing of the last pm_multi_mum_batch on this session (HIP events on the engine's stream):
  * names[i] / ms[i] for i < *count (count in: capacity, out: filled).  Used by bench.py's roofline line.

@@ -58,6 +58,23 @@ class Lib:
         self._check(self.L.pm_gap_limits_long(C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
 
+    def gap_limits_tall(self):
+        """(sequences, bases of a sequence, columns of an alignment) of the device gap aligner's tall form: pm_gap_limits_tall, the
+        limits of pm_gap_align_groups_tall (gaps of alignments with more than 512 genomes)"""
+        return self._gap_limits_of("pm_gap_limits_tall")
+
+    def gap_limits_long_tall(self):
+        """(sequences, bases of a sequence, columns of an alignment) of the device gap aligner's long-tall form: pm_gap_limits_long_tall,
+        the limits of pm_gap_align_groups_long_tall (more than 512 genomes and a cluster distance d of up to 1 000 at once)"""
+        return self._gap_limits_of("pm_gap_limits_long_tall")
+
+    def _gap_limits_of(self, name):
+        if not hasattr(self.L, name):
+            raise PmError("this provider of the ABI has no %s" % name)
+        a, b, c = C.c_int(), C.c_int(), C.c_int()
+        self._check(getattr(self.L, name)(C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
     def _check(self, rc):
         if rc != 0:
             raise PmError("%s (code %d)" % (self.L.pm_last_error().decode(), rc))

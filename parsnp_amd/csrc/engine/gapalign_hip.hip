@@ -1,5 +1,5 @@
 // gapalign_hip.hip -- the inter-MUM gap aligner on the MI355X: pm_gap_align_batch, pm_gap_align_groups,
-// pm_gap_align_groups_wide, pm_gap_align_groups_tall and pm_gap_align_groups_long (include/parsnp_mum.h).
+// pm_gap_align_groups_wide, pm_gap_align_groups_tall, pm_gap_align_groups_long and pm_gap_align_groups_long_tall (include/parsnp_mum.h).
 //
 // Replaces, for a whole run's worth of gaps at once, what the reference's XMFA writer does gap by gap:
 // MuscleInterface::CallMuscleFast (src/MuscleInterface.cpp:37-78, called at src/parsnp.cpp:854-855), i.e. the one
@@ -32,7 +32,9 @@
 // are bounded by the workspace they need (kTallWorkspace).  The fourth entry point adds it to what the third does.
 // The long form (kLongSeq = 1 024 bases, kLongCols = 2 048 columns, 512 sequences: every gap of a cluster distance d of up to 1 000)
 // is a kernel of its own, one alignment = one WORKGROUP of four wavefronts (align_job_long, below the others); the fifth entry
-// point adds it to what the third does.
+// point adds it to what the third does.  The long-tall form (kLongTallSeqs = 2 048 sequences with the long form's bases and columns)
+// is that kernel with its per-sequence arrays four times as long and the per-node weight totals in the slot's workspace
+// (SharedLongT); the sixth entry point takes the whole rectangle 2 048 x 1 024 and routes every job to one of the five forms.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -885,7 +887,8 @@ __global__ __launch_bounds__(64) void gap_align_kernel(Params P) {
 // (the DP cells grow with the square), so the stages that are loops over independent items run over all 256 threads, and the
 // pairwise DP -- three quarters of a wide job -- keeps four 64-row stripes of profile A in flight, one per wavefront (nw_long).
 // The arithmetic of every cell and every sum is align_job's, operation by operation; only who computes it differs.
-//   LDS (SharedLong, about 147 KB: one workgroup per CU)   the two profiles, the hand-over rings of the DP, the path and the
+//   LDS (SharedLong, about 147 KB; SharedLongTall, about 153 KB: one workgroup per CU)
+//                                                           the two profiles, the hand-over rings of the DP, the path and the
 //                                                           column maps, the per-sequence arrays
 //   slot workspace, through flat pointers                   the alignment rows, the trace-back bytes, the six sums of a profile
 //                                                           column before they are gathered, and what every form keeps there
@@ -904,8 +907,13 @@ constexpr size_t kLongAccBytes = (size_t)6 * 4 * kLongCols;
 // the lanes of ONE wavefront: their outstanding loads / stores have completed before any of them goes on
 #define GA_WAVE_SYNC() do { __builtin_amdgcn_s_waitcnt(0); __threadfence_block(); __builtin_amdgcn_wave_barrier(); } while (0)
 
-struct __align__(16) SharedLong {
-    static constexpr int kCols = kLongCols, kSeq = kLongSeq, kSeqs = kLongSeqs;
+// kSeqs_: the sequences of a job.  kTotalWs: the per-node weight totals lie in the slot's workspace (Slot::total), not in LDS -- the
+// long-tall form (kLongTallSeqs), whose per-sequence arrays would otherwise push the block past the LDS of a CU
+constexpr int kLongTallSeqs = 2048;
+template <int kSeqs_, bool kTotalWs_>
+struct __align__(16) SharedLongT {
+    static constexpr int kCols = kLongCols, kSeq = kLongSeq, kSeqs = kSeqs_;
+    static constexpr bool kTotalWs = kTotalWs_;
   union {           // the guide tree is finished (and synchronised on) before the first profile is built
     struct { float mind[kSeqs]; unsigned nearest[kSeqs]; unsigned node[kSeqs]; float height[kSeqs]; } t;      // tree
     struct {
@@ -923,7 +931,9 @@ struct __align__(16) SharedLong {
     } p;
   };
     uint8_t letter[256];       // alpha.cpp:125-166 (c_letter, copied)
-    float total_i[kSeqs];      // per internal node: sequential float sum of the weights of its rows, in row order
+    float total_i[kTotalWs_ ? 1 : kSeqs_];      // per internal node: sequential float sum of the weights of its rows, in row order
+    // (written once per node by thread 0 and read once per node after a barrier: the one per-sequence array that can leave the LDS)
+    __device__ float& total(const Slot& W, unsigned k) { if constexpr (kTotalWs_) return W.total[k]; else return total_i[k]; }
     uint16_t ncols_i[kSeqs];   // per internal node: columns of its alignment
     uint16_t rowlen[kSeqs];    // length of the sequence in row p
     uint16_t codes[kSeq];
@@ -932,13 +942,18 @@ struct __align__(16) SharedLong {
     int32_t flag;              // a value wavefront 0 (or thread 0) hands to everybody
     int32_t fail, wild;        // the job is given up / holds a wildcard
 };
+using SharedLong = SharedLongT<kLongSeqs, false>;
+using SharedLongTall = SharedLongT<kLongTallSeqs, true>;      // 2 048 sequences x 1 024 bases x 2 048 columns
+static_assert(sizeof(SharedLong) == 146496, "the long form's fixed block keeps its size");
 static_assert(sizeof(SharedLong) <= 160 * 1024 - 1024, "the long form's fixed block fits the LDS of a CU");
+static_assert(sizeof(SharedLongTall) <= 160 * 1024 - 1024, "the long-tall form's fixed block fits the LDS of a CU");
+static_assert(2 * kLongCols + 2 <= 32767, "a path's columns fit the 16-bit maps");
 static_assert(kLongCols + 2 <= 4096 && (kLongRing & (kLongRing - 1)) == 0, "hand-over masks");
 
 // build_profile over 256 threads: the (sum, column) items are spread over all threads, each sum still runs over the rows in MSA
 // order; the sums wait in the slot's workspace (ACC) until the columns are gathered
-template <bool kWild>
-__device__ void build_profile_long(SharedLong& S, const uint8_t* R, float* ACC, int cap, int lo, int ns, int nc, float total, bool as_a) {
+template <bool kWild, class Sh>
+__device__ void build_profile_long(Sh& S, const uint8_t* R, float* ACC, int cap, int lo, int ns, int nc, float total, bool as_a) {
     const int tid = (int)threadIdx.x;
     const float f = total != 0 ? 1.0f / total : 1.0f;
     const bool scale = total != 0;
@@ -1010,7 +1025,8 @@ __device__ void build_profile_long(SharedLong& S, const uint8_t* R, float* ACC, 
 // 256 columns later, two barriers after it was read.  The row from wavefront 3 to wavefront 0 is read a round later and is kept
 // whole; within a round wavefront 3 overwrites it six chunks behind wavefront 0's reads.  No wavefront polls memory: a wavefront
 // that has no chunk to do (not started yet, finished, or no rows left in the last round) goes straight to the barrier.
-__device__ bool nw_long(SharedLong& S, uint8_t* TB, int la, int lb, int* plen, bool prof, unsigned long long& prof_sweep, unsigned long long& prof_t0) {
+template <class Sh>
+__device__ bool nw_long(Sh& S, uint8_t* TB, int la, int lb, int* plen, bool prof, unsigned long long& prof_sweep, unsigned long long& prof_t0) {
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = uni(tid >> 6);
     const float e = kGapExtend;
     const int stride = lb + 1;
@@ -1142,11 +1158,11 @@ __device__ bool nw_long(SharedLong& S, uint8_t* TB, int la, int lb, int* plen, b
 }
 
 // align_job for a workgroup of kLongThreads threads (the comment above it tells why this is a call, not inlined)
+template <class Sh>
 #if !defined(PM_GAP_INLINE)
 __attribute__((noinline))
 #endif
-__device__ bool align_job_long(SharedLong& S, uint8_t* R, uint8_t* TB, float* ACC, const Slot& W, const Params& P, const Job& job, int* out_cols) {
-    using Sh = SharedLong;
+__device__ bool align_job_long(Sh& S, uint8_t* R, uint8_t* TB, float* ACC, const Slot& W, const Params& P, const Job& job, int* out_cols) {
     constexpr int T = kLongThreads;
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = uni(tid >> 6);
     const int n = uni(job.n), cap = uni(P.cap);      // (said uniform: every loop with a barrier in it is bounded by such values)
@@ -1414,8 +1430,8 @@ __device__ bool align_job_long(SharedLong& S, uint8_t* R, uint8_t* TB, float* AC
         const int loa = uni(__shfl(my_loa, k, 64)), nsa = uni(__shfl(my_nsa, k, 64)), lob = uni(__shfl(my_lob, k, 64)), nsb = uni(__shfl(my_nsb, k, 64));
         const int la = uni(a < un ? (int)S.rowlen[loa] : (int)S.ncols_i[a - un]);
         const int lb = uni(b < un ? (int)S.rowlen[lob] : (int)S.ncols_i[b - un]);
-        const float total_a = a < un ? 0.0f + S.wrow[loa] : S.total_i[a - un];
-        const float total_b = b < un ? 0.0f + S.wrow[lob] : S.total_i[b - un];
+        const float total_a = a < un ? 0.0f + S.wrow[loa] : S.total(W, a - un);
+        const float total_b = b < un ? 0.0f + S.wrow[lob] : S.total(W, b - un);
         if (la <= 0 || lb <= 0 || la > Sh::kCols || lb > Sh::kCols) return false;
         if (ga_stage_on(100)) GA_STAGE_DYN(100 + (int)(v - un) * 10);
         GA_CLOCK(8);
@@ -1488,7 +1504,7 @@ __device__ bool align_job_long(SharedLong& S, uint8_t* R, uint8_t* TB, float* AC
             S.ncols_i[v - un] = (uint16_t)plen;
             float t = total_a;                       // the merged alignment's rows: A's, then B's
             for (int x = 0; x < nsb; x++) t += S.wrow[lob + x];
-            S.total_i[v - un] = t;
+            S.total(W, v - un) = t;
         }
         GA_SYNC();
         GA_CLOCK(11);
@@ -1509,10 +1525,12 @@ __device__ bool align_job_long(SharedLong& S, uint8_t* R, uint8_t* TB, float* AC
 
 // the long form's kernel: a workgroup of four wavefronts per slot; the fixed block (SharedLong) is dynamic LDS, the rows, the
 // trace-back bytes and the profile sums lie in the slot's workspace
+// (Sh = SharedLong: the long form; Sh = SharedLongTall: the long-tall form, the same stages for up to kLongTallSeqs sequences)
+template <class Sh>
 __global__ __launch_bounds__(kLongThreads) void gap_align_long_kernel(Params P) {
     extern __shared__ __align__(16) uint8_t long_lds[];
     const Slot W = carve(P.ws + (size_t)blockIdx.x * (size_t)P.ws_stride, P.nmax, P.cap, kLongSeq, true, true);
-    SharedLong& S = *reinterpret_cast<SharedLong*>(long_lds);
+    Sh& S = *reinterpret_cast<Sh*>(long_lds);
     float* ACC = (float*)(W.tb + ((tb_bytes(P.cap) + 15) & ~(size_t)15));
     const int lane = (int)threadIdx.x;      // (the markers' name for the thread that writes them)
     for (int x = (int)threadIdx.x; x < 256; x += kLongThreads) S.letter[x] = c_letter[x];
@@ -1592,18 +1610,22 @@ extern "C" int64_t pm_gap_debug_peek(int32_t* out, int64_t cap) {
 }
 
 namespace {
-// One call of any of the five entry points.  level = 0: pm_gap_align_batch / pm_gap_align_groups, the narrow form alone, with the
+// One call of any of the six entry points.  level = 0: pm_gap_align_batch / pm_gap_align_groups, the narrow form alone, with the
 // limits and the launch they have always had.  level = 1: pm_gap_align_groups_wide -- a job with a sequence of more than kMaxCols
 // bases goes to the wide form, and a job the narrow form declined whose rows may be wider than kMaxCols is run again in the wide
 // form before its group is reported.  level = 2: pm_gap_align_groups_tall -- the same, and a job of more than kMaxSeqs sequences
 // goes to the tall form (which has the wide form's columns: nothing it declines would fare better in a second run).  level = 3:
 // pm_gap_align_groups_long -- what level 1 does, and a job with a sequence of more than kWideSeq bases goes to the long form.
-struct FormStats { int64_t jobs_narrow, jobs_wide, jobs_tall, jobs_long, declined; double ms_narrow, ms_wide, ms_tall, ms_long; };
+// level = 4: pm_gap_align_groups_long_tall -- what levels 2 and 3 do, and a job of more than kMaxSeqs sequences with a sequence of
+// more than kWideSeq bases goes to the long-tall form: the whole rectangle kLongTallSeqs x kLongSeq.
+struct FormStats { int64_t jobs_narrow, jobs_wide, jobs_tall, jobs_long, jobs_long_tall, declined; double ms_narrow, ms_wide, ms_tall, ms_long, ms_long_tall; };
+constexpr int kForms = 5;         // ranges of a group in the sorted job list: narrow, wide, tall, long, long-tall
+constexpr int kCounters = 6;      // queue counters of a group, one per launch: narrow, wide, wide again, tall, long, long-tall
 int align_groups(int level, int device, int64_t n_jobs, const int32_t* n_seqs, const int64_t* seq_off, const uint8_t* chars,
                  const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols,
                  int n_groups, const int64_t* group_end, void (*done)(void* ctx, int group), void* ctx, FormStats* stats) {
     const bool wide = level >= 1;
-    if (stats) *stats = FormStats{0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0};
+    if (stats) *stats = FormStats{0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0};
     if (n_jobs < 0 || (n_jobs > 0 && (!n_seqs || !seq_off || !chars || !max_cols || !row_off || !out_rows || !cols))) return fail(PM_EINVAL, "bad argument");
     if (n_groups < 1 || !group_end || group_end[n_groups - 1] != n_jobs) return fail(PM_EINVAL, "bad job groups");
     for (int g = 0; g < n_groups; g++) if (group_end[g] < (g ? group_end[g - 1] : 0)) return fail(PM_EINVAL, "bad job groups");
@@ -1638,13 +1660,13 @@ int align_groups(int level, int device, int64_t n_jobs, const int32_t* n_seqs, c
         }
         GA_CHECK(table_err);
     }
-    // jobs the device takes, per group the narrow ones, then the wide ones, then the tall ones, then the long ones, each longest first
+    // jobs the device takes, per group the narrow ones, then the wide ones, the tall ones, the long ones, the long-tall ones, each longest first
     // (the cost of one alignment grows with the square of its width)
     std::vector<Job> jobs; std::vector<int64_t> which; std::vector<int> group_of_job, form_of_job;
     int64_t seq = 0, total_chars = 0;
     int nmax = 2, cap = 1;             // of the narrow form: the widest job of the call
     std::vector<int> widest((size_t)n_jobs, 0);
-    const int seq_limit = level >= 3 ? kLongSeq : (wide ? kWideSeq : kMaxCols), seqs_limit = level == 2 ? kTallSeqs : kMaxSeqs;
+    const int seq_limit = level >= 3 ? kLongSeq : (wide ? kWideSeq : kMaxCols), seqs_limit = level == 2 ? kTallSeqs : (level == 4 ? kLongTallSeqs : kMaxSeqs);
     int grp = 0;
     for (int64_t j = 0; j < n_jobs; j++) {
         while (grp + 1 < n_groups && j >= group_end[grp]) grp++;
@@ -1655,17 +1677,18 @@ int align_groups(int level, int device, int64_t n_jobs, const int32_t* n_seqs, c
         if (ok && row_off[j] + (int64_t)n * max_cols[j] > out_bytes) ok = false;
         if (ok) {
             const int form = n > kMaxSeqs ? 2 : (w > kWideSeq ? 3 : (w > kMaxCols ? 1 : 0));
-            jobs.push_back(Job{seq, n, max_cols[j], row_off[j]}); which.push_back(j); group_of_job.push_back(grp); form_of_job.push_back(form); widest[(size_t)j] = w;
-            if (!form) { nmax = std::max(nmax, n); cap = std::max(cap, std::min<int>(max_cols[j], kMaxCols)); }
+            const int routed = form == 2 && w > kWideSeq ? 4 : form;      // more than kMaxSeqs sequences AND a string above kWideSeq (level 4 alone lets one through): the long-tall form
+            jobs.push_back(Job{seq, n, max_cols[j], row_off[j]}); which.push_back(j); group_of_job.push_back(grp); form_of_job.push_back(routed); widest[(size_t)j] = w;
+            if (!routed) { nmax = std::max(nmax, n); cap = std::max(cap, std::min<int>(max_cols[j], kMaxCols)); }
         }
         seq += n;
     }
     total_chars = seq_off[seq];
     auto count_declined = [&]() { if (stats) { stats->declined = 0; for (int64_t j = 0; j < n_jobs; j++) stats->declined += cols[j] < 0; } };
     if (jobs.empty()) { count_declined(); all_done(0); return PM_OK; }
-    // in the sorted job list: group g = [first[4g], first[4g+4]), its narrow jobs first, its wide jobs from first[4g+1], its tall
-    // jobs from first[4g+2], its long jobs from first[4g+3]
-    std::vector<size_t> first((size_t)n_groups * 4 + 1, 0);
+    // in the sorted job list: group g = [first[5g], first[5g+5]), its narrow jobs first, its wide jobs from first[5g+1], its tall
+    // jobs from first[5g+2], its long jobs from first[5g+3], its long-tall jobs from first[5g+4]
+    std::vector<size_t> first((size_t)n_groups * kForms + 1, 0);
     {
         std::vector<size_t> order(jobs.size());
         for (size_t i = 0; i < order.size(); i++) order[i] = i;
@@ -1675,8 +1698,8 @@ int align_groups(int level, int device, int64_t n_jobs, const int32_t* n_seqs, c
             return widest[(size_t)which[a]] > widest[(size_t)which[b]];
         });
         std::vector<Job> j2; std::vector<int64_t> w2;
-        for (size_t i : order) { j2.push_back(jobs[i]); w2.push_back(which[i]); first[(size_t)group_of_job[i] * 4 + (size_t)form_of_job[i] + 1]++; }
-        for (size_t k = 0; k < (size_t)n_groups * 4; k++) first[k + 1] += first[k];
+        for (size_t i : order) { j2.push_back(jobs[i]); w2.push_back(which[i]); first[(size_t)group_of_job[i] * kForms + (size_t)form_of_job[i] + 1]++; }
+        for (size_t k = 0; k < (size_t)n_groups * kForms; k++) first[k + 1] += first[k];
         jobs.swap(j2); which.swap(w2);
     }
     const bool timers = getenv("PARSNP_DEBUG_TIMERS") != nullptr;
@@ -1688,7 +1711,7 @@ int align_groups(int level, int device, int64_t n_jobs, const int32_t* n_seqs, c
     GA_CHECK(hipGetDeviceProperties(&prop, device));
     GA_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     auto dalloc = [&](size_t bytes, void** p) { hipError_t e = hipMalloc(p, bytes ? bytes : 1); if (e == hipSuccess) owned.push_back(*p); return e; };
-    const bool any_narrow = [&] { for (int g = 0; g < n_groups; g++) if (first[(size_t)g * 4 + 1] > first[(size_t)g * 4]) return true; return false; }();
+    const bool any_narrow = [&] { for (int g = 0; g < n_groups; g++) if (first[(size_t)g * kForms + 1] > first[(size_t)g * kForms]) return true; return false; }();
     // ---- the narrow form.  LDS of a workgroup: the fixed block plus the alignment rows of the widest job and the trace-back bytes;
     // as many workgroups per CU as fit in 160 KB
     constexpr size_t kLdsLimit = 160 * 1024 - 1024;
@@ -1701,7 +1724,7 @@ int align_groups(int level, int device, int64_t n_jobs, const int32_t* n_seqs, c
         if (lds > 64 * 1024) GA_CHECK(hipFuncSetAttribute((const void*)gap_align_kernel<Shared>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rows_lds));
         per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / (lds + 256)));
         size_t most = 0;      // narrow jobs of one group (without a wide job in the call: of the call, as the launch has always been sized)
-        for (int g = 0; g < n_groups; g++) most = std::max(most, first[(size_t)g * 4 + 1] - first[(size_t)g * 4]);
+        for (int g = 0; g < n_groups; g++) most = std::max(most, first[(size_t)g * kForms + 1] - first[(size_t)g * kForms]);
         slots = std::min<int64_t>(wide ? (int64_t)most : (int64_t)jobs.size(), (int64_t)prop.multiProcessorCount * per_cu);
         stride = slot_bytes(nmax, cap, kMaxCols, false, false);
     }
@@ -1711,12 +1734,12 @@ int align_groups(int level, int device, int64_t n_jobs, const int32_t* n_seqs, c
     GA_CHECK(dalloc((size_t)total_chars, (void**)&d_chars));
     GA_CHECK(dalloc((size_t)out_bytes, (void**)&d_out));
     GA_CHECK(dalloc(4 * jobs.size(), (void**)&d_cols));
-    GA_CHECK(dalloc(8 * 5 * (size_t)n_groups, (void**)&d_next));      // a queue counter per launch: narrow, wide, wide again, tall, long
+    GA_CHECK(dalloc(8 * kCounters * (size_t)n_groups, (void**)&d_next));      // a queue counter per launch: narrow, wide, wide again, tall, long, long-tall
     if (any_narrow) GA_CHECK(dalloc(stride * (size_t)slots, (void**)&d_ws));
     GA_CHECK(hipMemcpyAsync(d_jobs, jobs.data(), sizeof(Job) * jobs.size(), hipMemcpyHostToDevice, stream));
     GA_CHECK(hipMemcpyAsync(d_off, seq_off, 8 * (size_t)(seq + 1), hipMemcpyHostToDevice, stream));
     GA_CHECK(hipMemcpyAsync(d_chars, chars, (size_t)total_chars, hipMemcpyHostToDevice, stream));
-    GA_CHECK(hipMemsetAsync(d_next, 0, 8 * 5 * (size_t)n_groups, stream));
+    GA_CHECK(hipMemsetAsync(d_next, 0, 8 * kCounters * (size_t)n_groups, stream));
     if (timers) { GA_CHECK(hipStreamSynchronize(stream)); lap("alloc + h2d"); }
     int32_t* dbg = nullptr;
     const int64_t dbg_slots = std::max<int64_t>(slots, wide ? (int64_t)prop.multiProcessorCount * 8 : 0);
@@ -1782,11 +1805,13 @@ int align_groups(int level, int device, int64_t n_jobs, const int32_t* n_seqs, c
     };
     // ---- the long form: a workgroup of four wavefronts per slot, one per CU (its fixed block takes most of the LDS); rows, trace-back
     // bytes and profile sums in the slot's workspace, which also bounds the slots (kLongWorkspace).  Shares the wide launches' workspace.
-    auto launch_long = [&](const Job* host_jobs, size_t nj, const Job* dev_jobs, int32_t* dev_cols, unsigned long long* counter) -> hipError_t {
+    // (tall: the long-tall form -- the same launch with SharedLongTall as its fixed block; a slot of 2 048 x 2 048 needs 31 MB)
+    auto launch_long = [&](bool tall, const Job* host_jobs, size_t nj, const Job* dev_jobs, int32_t* dev_cols, unsigned long long* counter) -> hipError_t {
+        void (*const kernel)(Params) = tall ? gap_align_long_kernel<SharedLongTall> : gap_align_long_kernel<SharedLong>;
         int wn = 2, wc = 1;
         for (size_t i = 0; i < nj; i++) { wn = std::max(wn, host_jobs[i].n); wc = std::max(wc, std::min<int>(host_jobs[i].max_cols, kLongCols)); }
-        const size_t dyn = (sizeof(SharedLong) + 15) & ~(size_t)15;
-        hipError_t e = hipFuncSetAttribute((const void*)gap_align_long_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
+        const size_t dyn = ((tall ? sizeof(SharedLongTall) : sizeof(SharedLong)) + 15) & ~(size_t)15;
+        hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
         if (e != hipSuccess) return e;
         const size_t wstride = slot_bytes(wn, wc, kLongSeq, true, true) + kLongAccBytes;
         const int64_t wslots = std::min<int64_t>(std::min<int64_t>((int64_t)nj, (int64_t)prop.multiProcessorCount), std::max<int64_t>(1, (int64_t)(kLongWorkspace / wstride)));
@@ -1798,12 +1823,12 @@ int align_groups(int level, int device, int64_t n_jobs, const int32_t* n_seqs, c
             if (e != hipSuccess) return e;
             wide_ws_bytes = wstride * (size_t)wslots;
         }
-        if (timers) fprintf(stderr, "[gap batch] long form: %zu jobs, widest %d sequences x %d columns: %zu B of LDS per workgroup of %d threads (rows, trace-back and profile sums in the workspace), 1 per CU, %lld slots, %.1f MB of workspace\n",
-                            nj, wn, wc, dyn, kLongThreads, (long long)wslots, (double)(wstride * (size_t)wslots) / 1048576.0);
+        if (timers) fprintf(stderr, "[gap batch] %s form: %zu jobs, widest %d sequences x %d columns: %zu B of LDS per workgroup of %d threads (rows, trace-back and profile sums in the workspace), 1 per CU, %lld slots, %.1f MB of workspace\n",
+                            tall ? "long-tall" : "long", nj, wn, wc, dyn, kLongThreads, (long long)wslots, (double)(wstride * (size_t)wslots) / 1048576.0);
         Params P{dev_jobs, (int64_t)nj, d_off, d_chars, d_out, dev_cols, counter, d_wide_ws, (int64_t)wstride, wn, wc, 1, 1, dbg, d_prof};
-        Timed t{nullptr, nullptr, 3};
+        Timed t{nullptr, nullptr, tall ? 4 : 3};
         if (stats && (e = mark(&t.a)) != hipSuccess) return e;
-        hipLaunchKernelGGL(gap_align_long_kernel, dim3((unsigned)wslots), dim3(kLongThreads), dyn, stream, P);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)wslots), dim3(kLongThreads), dyn, stream, P);
         if ((e = hipGetLastError()) != hipSuccess) return e;
         if (stats) { if ((e = mark(&t.b)) != hipSuccess) return e; timed.push_back(t); }
         return hipSuccess;
@@ -1812,11 +1837,12 @@ int align_groups(int level, int device, int64_t n_jobs, const int32_t* n_seqs, c
     std::vector<Job> again; std::vector<size_t> again_at; std::vector<int32_t> again_got;
     std::vector<std::pair<int64_t, int64_t>> spans;
     for (int g = 0; g < n_groups; g++) {
-        const size_t j0 = first[(size_t)g * 4], jw = first[(size_t)g * 4 + 1], jt = first[(size_t)g * 4 + 2], jl = first[(size_t)g * 4 + 3], j1 = first[(size_t)g * 4 + 4];
+        const size_t j0 = first[(size_t)g * kForms], jw = first[(size_t)g * kForms + 1], jt = first[(size_t)g * kForms + 2], jl = first[(size_t)g * kForms + 3],
+                     jx = first[(size_t)g * kForms + 4], j1 = first[(size_t)g * kForms + 5];
         if (j1 > j0) {
             if (jw > j0) {
                 // a group's jobs: their own queue counter, their slice of the job and column arrays; workspace and slots shared
-                Params P{d_jobs + j0, (int64_t)(jw - j0), d_off, d_chars, d_out, d_cols + j0, d_next + 5 * g, d_ws, (int64_t)stride, nmax, cap, 0, 0, dbg, d_prof};
+                Params P{d_jobs + j0, (int64_t)(jw - j0), d_off, d_chars, d_out, d_cols + j0, d_next + kCounters * g, d_ws, (int64_t)stride, nmax, cap, 0, 0, dbg, d_prof};
                 const int64_t gslots = std::min<int64_t>((int64_t)(jw - j0), slots);
                 Timed t{nullptr, nullptr, 0};
                 if (stats) GA_CHECK(mark(&t.a));
@@ -1824,9 +1850,10 @@ int align_groups(int level, int device, int64_t n_jobs, const int32_t* n_seqs, c
                 GA_CHECK(hipGetLastError());
                 if (stats) { GA_CHECK(mark(&t.b)); timed.push_back(t); }
             }
-            if (jt > jw) GA_CHECK(launch_wide(1, jobs.data() + jw, jt - jw, d_jobs + jw, d_cols + jw, d_next + 5 * g + 1));
-            if (jl > jt) GA_CHECK(launch_wide(2, jobs.data() + jt, jl - jt, d_jobs + jt, d_cols + jt, d_next + 5 * g + 3));
-            if (j1 > jl) GA_CHECK(launch_long(jobs.data() + jl, j1 - jl, d_jobs + jl, d_cols + jl, d_next + 5 * g + 4));
+            if (jt > jw) GA_CHECK(launch_wide(1, jobs.data() + jw, jt - jw, d_jobs + jw, d_cols + jw, d_next + kCounters * g + 1));
+            if (jl > jt) GA_CHECK(launch_wide(2, jobs.data() + jt, jl - jt, d_jobs + jt, d_cols + jt, d_next + kCounters * g + 3));
+            if (jx > jl) GA_CHECK(launch_long(false, jobs.data() + jl, jx - jl, d_jobs + jl, d_cols + jl, d_next + kCounters * g + 4));
+            if (j1 > jx) GA_CHECK(launch_long(true, jobs.data() + jx, j1 - jx, d_jobs + jx, d_cols + jx, d_next + kCounters * g + 5));
             GA_CHECK(hipMemcpyAsync(got.data() + j0, d_cols + j0, 4 * (j1 - j0), hipMemcpyDeviceToHost, stream));
             if (!wide) GA_CHECK(hipStreamSynchronize(stream));
             if (wide) {
@@ -1837,7 +1864,7 @@ int align_groups(int level, int device, int64_t n_jobs, const int32_t* n_seqs, c
                 if (!again.empty()) {
                     if (!d_again) { GA_CHECK(dalloc(sizeof(Job) * jobs.size(), (void**)&d_again)); GA_CHECK(dalloc(4 * jobs.size(), (void**)&d_again_cols)); }
                     GA_CHECK(hipMemcpyAsync(d_again, again.data(), sizeof(Job) * again.size(), hipMemcpyHostToDevice, stream));
-                    GA_CHECK(launch_wide(1, again.data(), again.size(), d_again, d_again_cols, d_next + 5 * g + 2));
+                    GA_CHECK(launch_wide(1, again.data(), again.size(), d_again, d_again_cols, d_next + kCounters * g + 2));
                     again_got.resize(again.size());
                     GA_CHECK(hipMemcpyAsync(again_got.data(), d_again_cols, 4 * again.size(), hipMemcpyDeviceToHost, stream));
                     GA_CHECK(hipStreamSynchronize(stream));
@@ -1860,12 +1887,13 @@ int align_groups(int level, int device, int64_t n_jobs, const int32_t* n_seqs, c
             GA_CHECK(hipStreamSynchronize(stream));
             for (size_t i = j0; i < j1; i++) cols[which[i]] = got[i];
             if (stats) { for (size_t i = j0; i < jw; i++) stats->jobs_narrow += got[i] >= 0; for (size_t i = jw; i < jt; i++) stats->jobs_wide += got[i] >= 0;
-                         for (size_t i = jt; i < jl; i++) stats->jobs_tall += got[i] >= 0; for (size_t i = jl; i < j1; i++) stats->jobs_long += got[i] >= 0; }
+                         for (size_t i = jt; i < jl; i++) stats->jobs_tall += got[i] >= 0; for (size_t i = jl; i < jx; i++) stats->jobs_long += got[i] >= 0;
+                         for (size_t i = jx; i < j1; i++) stats->jobs_long_tall += got[i] >= 0; }
         }
         if (timers) { char what[32]; snprintf(what, sizeof what, "group %d", g + 1); lap(what); }
         if (done) done(ctx, g);
     }
-    for (const Timed& t : timed) { float ms = 0; if (hipEventElapsedTime(&ms, t.a, t.b) == hipSuccess) (t.form == 3 ? stats->ms_long : (t.form == 2 ? stats->ms_tall : (t.form ? stats->ms_wide : stats->ms_narrow))) += (double)ms; }
+    for (const Timed& t : timed) { float ms = 0; if (hipEventElapsedTime(&ms, t.a, t.b) == hipSuccess) (t.form == 4 ? stats->ms_long_tall : t.form == 3 ? stats->ms_long : (t.form == 2 ? stats->ms_tall : (t.form ? stats->ms_wide : stats->ms_narrow))) += (double)ms; }
     count_declined();
     if (d_prof) {
         unsigned long long prof[kProfStages];
@@ -1923,6 +1951,22 @@ extern "C" int pm_gap_align_groups_long(int device, int64_t n_jobs, const int32_
     const int rc = align_groups(3, device, n_jobs, n_seqs, seq_off, chars, max_cols, row_off, out_rows, out_bytes, cols, n_groups, group_end, done, ctx, stats ? &all : nullptr);
     if (stats) *stats = pm_gap_long_stats{all.jobs_narrow, all.jobs_wide, all.jobs_long, all.declined, all.ms_narrow, all.ms_wide, all.ms_long};
     return rc;
+}
+// ... and with the long-tall form beside the other four: the limits of pm_gap_limits_long_tall
+extern "C" int pm_gap_align_groups_long_tall(int device, int64_t n_jobs, const int32_t* n_seqs, const int64_t* seq_off, const uint8_t* chars,
+                                             const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols,
+                                             int n_groups, const int64_t* group_end, void (*done)(void* ctx, int group), void* ctx, pm_gap_long_tall_stats* stats) {
+    FormStats all;
+    const int rc = align_groups(4, device, n_jobs, n_seqs, seq_off, chars, max_cols, row_off, out_rows, out_bytes, cols, n_groups, group_end, done, ctx, stats ? &all : nullptr);
+    if (stats) *stats = pm_gap_long_tall_stats{all.jobs_narrow, all.jobs_wide, all.jobs_tall, all.jobs_long, all.jobs_long_tall, all.declined,
+                                               all.ms_narrow, all.ms_wide, all.ms_tall, all.ms_long, all.ms_long_tall};
+    return rc;
+}
+extern "C" int pm_gap_limits_long_tall(int* max_seqs, int* max_seq_len, int* max_cols) {
+    if (max_seqs) *max_seqs = kLongTallSeqs;
+    if (max_seq_len) *max_seq_len = kLongSeq;
+    if (max_cols) *max_cols = kLongCols;
+    return PM_OK;
 }
 extern "C" int pm_gap_limits_long(int* max_seqs, int* max_seq_len, int* max_cols) {
     if (max_seqs) *max_seqs = kLongSeqs;

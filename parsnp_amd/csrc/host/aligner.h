@@ -470,9 +470,10 @@ struct GapCounts {
     long device_narrow = 0, device_wide = 0;      // aligned by the device's narrow / wide form
     long device_tall = 0;          // ... and by its tall form (alignments of more than 512 genomes)
     long device_long = 0;          // ... and by its long form (a string of more than 320 bases)
+    long device_long_tall = 0;     // ... and by its long-tall form (both: more than 512 genomes and a string of more than 320 bases)
     long host = 0;                 // aligned by the host restatement (gapalign.cpp)
     double host_s = 0;             // ... in this many seconds, summed over the threads
-    double device_narrow_ms = 0, device_wide_ms = 0, device_tall_ms = 0, device_long_ms = 0;      // kernel time of each form
+    double device_narrow_ms = 0, device_wide_ms = 0, device_tall_ms = 0, device_long_ms = 0, device_long_tall_ms = 0;      // kernel time of each form
 };
 extern GapCounts gap_counts;
 // XMFA + log (writeOutput).  gap_note: set when the gap aligner (gapalign.h) declined an inter-MUM gap and it was written '-'-padded.

@@ -144,7 +144,7 @@ int main(int argc, char* argv[]) {
                     "\"gap_note\": %s, \"tie_fallbacks\": %ld, \"literal_iterations\": %ld, \"parallel_candidates\": %ld, \"parallel_dirty\": %ld, \"t_validate\": %.6f, \"t_neighbour\": %.6f, \"t_sweep\": %.6f, \"t_replay\": %.6f, \"t_key\": %.6f, \"resident\": %ld, \"resident_retry\": %ld, \"device_chain\": %ld, \"h2d_bytes\": %.0f, \"d2h_bytes\": %.0f, \"outside_writes\": %.0f, \"dense_regions\": %.0f, \"resident_why\": \"%s\", "
                     "\"gap_jobs\": %ld, \"gap_jobs_wide\": %ld, \"gap_longest\": %ld, \"gap_device_narrow\": %ld, \"gap_device_wide\": %ld, \"gap_host\": %ld, \"gap_host_s\": %.6f, "
                     "\"gap_device_narrow_ms\": %.3f, \"gap_device_wide_ms\": %.3f, \"gap_device_tall\": %ld, \"gap_device_tall_ms\": %.3f, "
-                    "\"gap_jobs_long\": %ld, \"gap_device_long\": %ld, \"gap_device_long_ms\": %.3f}\n",
+                    "\"gap_jobs_long\": %ld, \"gap_device_long\": %ld, \"gap_device_long_ms\": %.3f, \"gap_device_long_tall\": %ld, \"gap_device_long_tall_ms\": %.3f}\n",
                     pm_provider(), run.genomes.size(), run.qfiles, run.ingest_s, run.upload_s, rep.path_s, rep.anchor_s, rep.extend_s, rep.filter_s,
                     rep.lcb_s, output_s, now_s() - t_begin, rep.finder_s, rep.finder_calls, rep.finder_regions, rep.regions_processed,
                     rep.cache_hits, rep.cache_misses, rep.spec_rounds, rep.anchors, rep.mums, rep.lcbs, rep.core_bp, gap_note ? "true" : "false",
@@ -152,7 +152,7 @@ int main(int argc, char* argv[]) {
                     rep.host.resident, rep.host.resident_retry, rep.host.device_chain, rep.h2d_bytes, rep.d2h_bytes, outside_writes, dense_regions, why.c_str(),
                     gap_counts.jobs, gap_counts.jobs_wide, gap_counts.longest, gap_counts.device_narrow, gap_counts.device_wide, gap_counts.host, gap_counts.host_s,
                     gap_counts.device_narrow_ms, gap_counts.device_wide_ms, gap_counts.device_tall, gap_counts.device_tall_ms,
-                    gap_counts.jobs_long, gap_counts.device_long, gap_counts.device_long_ms);
+                    gap_counts.jobs_long, gap_counts.device_long, gap_counts.device_long_ms, gap_counts.device_long_tall, gap_counts.device_long_tall_ms);
             fclose(f);
         }
     }

@@ -76,7 +76,8 @@ def read_timing(path):
     search and, for the gaps between adjacent MUMs that the writer aligned, gap_jobs, gap_jobs_wide (a string of more than 96
     bases), gap_longest, gap_device_narrow / gap_device_wide / gap_device_tall (aligned by the device's narrow, wide and tall
     form -- the last takes the gaps of alignments with more than 512 genomes --, with gap_device_*_ms of kernel time), gap_host and gap_host_s (aligned by the host restatement);
-    gap_jobs_long (a string of more than 320 bases: a cluster distance above the default) and gap_device_long / gap_device_long_ms (the device's long form)"""
+    gap_jobs_long (a string of more than 320 bases: a cluster distance above the default) and gap_device_long / gap_device_long_ms (the device's long form);
+    gap_device_long_tall / gap_device_long_tall_ms (its long-tall form: more than 512 genomes and a string of more than 320 bases at once)"""
     import json
     with open(path) as f:
         return json.load(f)

@@ -274,6 +274,8 @@ CONFIGS = {
     # jobs of the device gap aligner's long form (at the default d = 300 such a window ends the cluster instead)
     "long10x300k": ("population", dict(seed=51, n=300_000, n_genomes=10, div=0.01, indel_frac=0.05, windows=dict(count=60, min_len=330, max_len=900))),
     "long200x150k": ("population", dict(seed=53, n=150_000, n_genomes=200, div=0.01, indel_frac=0.05, windows=dict(count=30, haplotypes=24, min_len=330, max_len=900))),
+    # ... and with more than 511 query genomes: every gap has 601 sequences, the jobs of the long-tall form
+    "longtall600x60k": ("population", dict(seed=73, n=60_000, n_genomes=600, div=0.01, indel_frac=0.05, windows=dict(count=6, haplotypes=24, min_len=330, max_len=900))),
     "poprearr10x400k": ("pop_rearranged", dict(seed=13, n=400_000, n_genomes=10, div=0.05, frac=0.10)),
 }
 
