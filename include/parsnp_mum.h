@@ -156,6 +156,10 @@ int64_t pm_result_table_id(const pm_result* r);
  *   "atomic_marks" != 0: pm_store_settle marks the layout with atomic ORs even where the list's order allows plain stores (tests)
  *   "group_small"  0: the events of a recursion batch's small regions are found pair by pair and sorted with the others, instead of
  *                  once per distinct query piece (default 1; both give the same events, tests compare the two)
+ *   "group_wide"   != 0: the small regions that form does not take -- more than 32 distinct pieces, more than 8 events of one (piece,
+ *                  strand), a batch of more than 1 024 query genomes -- are taken by its wide form up to the limits of
+ *                  pm_group_limits(1), instead of pair by pair (default 0: as measured the wide form costs more than it saves,
+ *                  DESIGN.md 8; never on while "group_small" is 0; the same events either way, tests compare the two)
  *   "slot_factor"  index slots per reference position before rounding up to a power of two (default 2: load <= 1/2; 1 = rounds 1-5,
  *                  load <= 2/3 -- the wavefronts of IndexInsert and of the probes run as long as their longest probe sequence);
  *   "filter_factor" presence-filter bits per reference position before rounding up (default 8; 4 ... 32 measured: flat)
@@ -447,6 +451,13 @@ int pm_gap_limits_long_tall(int* max_seqs, int* max_seq_len, int* max_cols);
  * events), and "dense_overrun" (wall ms of the pass that ran out of budget before it; not with "dense_all").  Other calls
  * report none of these keys. */
 int pm_last_timing(const pm_session* s, int* count, const char** names, float* ms);
+
+/* The limits of the kernels that find the events of a recursion batch's small regions (every side at most 128 bases) once per
+ * distinct query piece: distinct pieces of a region, events of one (piece, strand), query genomes of the batch.  wide = 0: the
+ * first form (32, 8, 1 024); wide != 0: the wide form (128, 32, 2 047), which takes what the first leaves when "group_wide" is set.  A
+ * region beyond both is searched pair by pair; pm_last_timing counts them ("n_handed_back"; "n_grouped_wide": the events the wide
+ * form wrote).  Any pointer may be NULL. */
+int pm_group_limits(int wide, int* max_pieces, int* max_events, int* max_genomes);
 
 #ifdef __cplusplus
 }

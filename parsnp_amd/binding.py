@@ -68,6 +68,15 @@ class Lib:
         the limits of pm_gap_align_groups_long_tall (more than 512 genomes and a cluster distance d of up to 1 000 at once)"""
         return self._gap_limits_of("pm_gap_limits_long_tall")
 
+    def group_limits(self, wide=True):
+        """(distinct pieces of a region, events of one (piece, strand), query genomes of a batch) of the kernels that find the events of
+        small regions once per distinct piece: pm_group_limits -- wide: the wide form's, else the first form's"""
+        if not hasattr(self.L, "pm_group_limits"):
+            raise PmError("this provider of the ABI has no pm_group_limits")
+        a, b, c = C.c_int(), C.c_int(), C.c_int()
+        self._check(self.L.pm_group_limits(C.c_int(1 if wide else 0), C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
     def _gap_limits_of(self, name):
         if not hasattr(self.L, name):
             raise PmError("this provider of the ABI has no %s" % name)
@@ -122,7 +131,7 @@ class Session:
             self.h = None
 
     def tune(self, key: str, value: int):
-        """pm_session_tune: "work_budget", "dirty_min" (include/parsnp_mum.h)"""
+        """pm_session_tune: "work_budget", "dirty_min", "group_small", "group_wide", ... (include/parsnp_mum.h)"""
         self.lib.L.pm_session_tune.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
         self.lib._check(self.lib.L.pm_session_tune(self.h, key.encode(), value))
 

@@ -309,6 +309,13 @@ int pm_mumi_coverage(pm_session* s, const int64_t* starts, const int64_t* lens, 
     } catch (const pm::Engine<PmBackend>::DeviceOutOfMemory& e) { return fail(PM_ENOMEM, "device allocation of " + std::to_string(e.bytes) + " bytes failed"); }
 }
 
+int pm_group_limits(int wide, int* max_pieces, int* max_events, int* max_genomes) {
+    if (max_pieces) *max_pieces = wide ? pm::kWidePieces : pm::kGrpPieces;
+    if (max_events) *max_events = wide ? pm::kWideEvents : pm::kGrpEvents;
+    if (max_genomes) *max_genomes = wide ? pm::kWideGenomes : pm::kGrpGenomes;
+    return PM_OK;
+}
+
 int pm_last_timing(const pm_session* cs, int* count, const char** names, float* ms) {
     if (!cs || !count) return PM_EINVAL;
     pm_session* s = const_cast<pm_session*>(cs);
@@ -330,6 +337,9 @@ int pm_last_timing(const pm_session* cs, int* count, const char** names, float* 
     s->timing.push_back(pm::PhaseTime{"n_candidates", (float)s->engine->last_candidates});
     s->timing.push_back(pm::PhaseTime{"n_accepted", (float)s->engine->last_accepted});
     s->timing.push_back(pm::PhaseTime{"n_grouped", (float)s->engine->last_grouped});
+    s->timing.push_back(pm::PhaseTime{"n_grouped_wide", (float)s->engine->last_grouped_wide});      // of n_grouped, the events the wide form wrote
+    s->timing.push_back(pm::PhaseTime{"n_wide_regions", (float)s->engine->last_wide_regions});      // regions the wide form took
+    s->timing.push_back(pm::PhaseTime{"n_handed_back", (float)s->engine->last_handed_back});        // small regions neither form took (-1: the wide form, which counts them, did not run)
     if (s->engine->outside_writes) { s->timing.push_back(pm::PhaseTime{"outside_writes", (float)s->engine->outside_writes}); s->engine->outside_writes = 0; }      // accepted members outside their region, checked against the order (OutsideWriteCheck)
     if (s->engine->exact_cluster_tests) { s->timing.push_back(pm::PhaseTime{"exact_cluster_tests", (float)s->engine->exact_cluster_tests}); s->engine->exact_cluster_tests = 0; }      // generations validated with the exact test of their clusters (inversions)
     if (s->engine->tail_repeats) { s->timing.push_back(pm::PhaseTime{"tail_repeats", (float)s->engine->tail_repeats}); s->engine->tail_repeats = 0; }      // searches that repeated a part because a capacity from the last step was too small

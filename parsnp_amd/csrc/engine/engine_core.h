@@ -315,7 +315,7 @@ public:
             nunits += units_r[(size_t)r];
         }
         posbase[regz] = npos;
-        last_positions = npos; last_candidates = 0; last_accepted = 0; last_grouped = 0;
+        last_positions = npos; last_candidates = 0; last_accepted = 0; last_grouped = 0; last_grouped_wide = 0; last_handed_back = -1; last_wide_regions = 0;
         const int64_t npairs = nreg * nq;
         const int64_t nchunks = cbase[regz] - nreg;                  // 256-position chunks of the batch
         const int64_t centries = cbase[regz] * nq;
@@ -432,8 +432,13 @@ public:
         uint32_t sticky = 0;
         std::vector<uint64_t> qcounts((size_t)kSlices * kSliceStride);
         // the small regions of a recursion batch: their events once per distinct piece, straight into the head of the final array
-        const bool grouping = group_small && !no_small && !want_events && nreg >= 2 && nq <= kGrpGenomes;
+        // (the first form up to kGrpGenomes query genomes; the wide form after it over the regions it left, or alone up to kWideGenomes)
+        const bool small_groups = group_small && !no_small && !want_events && nreg >= 2;
+        const bool first_form = small_groups && nq <= kGrpGenomes;
+        const bool wide_form = small_groups && group_wide && nq <= kWideGenomes;
+        const bool grouping = first_form || wide_form;
         const size_t kGrpSlot = (size_t)kSlices * kSliceStride + 2;      // (d_counter: the block counter of the grouped events)
+        const size_t kWideSlot = kGrpSlot + 1;                           // (... and the wide form's counts: events, regions handed back, regions taken)
         size_t grp_cap = grouping ? std::max<size_t>(grp_cap_hint, (size_t)npairs * 3) + 64 : 0;
         uint64_t ngrp = 0;
         if (grouping) { ensure(d_gflag, (size_t)nreg); ensure(d_glo, (size_t)npairs); }
@@ -448,9 +453,14 @@ public:
                 ensure(d_evkey3, grp_cap + ev_cap_hint); ensure(d_evval3, grp_cap + ev_cap_hint);
                 ensure(d_state, grp_cap + ev_cap_hint); ensure(d_emax, grp_cap + ev_cap_hint);
                 be.mark("grouped_events");
-                be.launch_wave("grouped_pair_events", xcd_grid(nreg),
-                               GroupedPairEvents{P, d_R.p, d_starts.p, d_lens.p, ngen, d_rep.p, d_evkey3.p, d_evval3.p, d_counter.p + kGrpSlot, (uint64_t)grp_cap, lbits,
-                                                 d_glo.p, g_first, g_last, d_gflag.p, d_state.p, d_emax.p, d_epm.p, (int64_t)nreg});
+                if (first_form)
+                    be.launch_wave("grouped_pair_events", xcd_grid(nreg),
+                                   GroupedPairEvents{P, d_R.p, d_starts.p, d_lens.p, ngen, d_rep.p, d_evkey3.p, d_evval3.p, d_counter.p + kGrpSlot, (uint64_t)grp_cap, lbits,
+                                                     d_glo.p, g_first, g_last, d_gflag.p, d_state.p, d_emax.p, d_epm.p, (int64_t)nreg});
+                if (wide_form)
+                    be.launch_wave("grouped_pair_events_wide", xcd_grid(nreg),
+                                   GroupedPairEventsWide{P, d_R.p, d_starts.p, d_lens.p, ngen, d_rep.p, d_evkey3.p, d_evval3.p, d_counter.p + kGrpSlot, (uint64_t)grp_cap, lbits,
+                                                         d_glo.p, g_first, g_last, d_gflag.p, d_state.p, d_emax.p, d_epm.p, (int64_t)nreg, first_form ? 1 : 0, d_counter.p + kWideSlot});
             }
             be.memset(d_qcount.p, 0, 8 * (size_t)kSlices * kSliceStride);
             be.mark("seed_extend");
@@ -518,6 +528,9 @@ public:
         if (grouping) grp_cap_hint = (size_t)(ngrp + ngrp / 4);
         last_events = (int64_t)(nev + ngrp);
         last_grouped = (int64_t)ngrp;
+        last_grouped_wide = wide_form ? (int64_t)counts[kWideSlot] : 0;
+        last_handed_back = wide_form ? (int64_t)counts[kWideSlot + 1] : -1;      // (-1: nobody counted them -- the wide form did not run)
+        last_wide_regions = wide_form ? (int64_t)counts[kWideSlot + 2] : 0;
         // a rank of a sharded run that ran out of budget must not leave the others waiting in the collectives: the
         // verdict travels with the first exchange (below) and every rank returns the error together
         const bool sharded = coll.world > 1 || coll.device;      // (a one-rank RCCL session still runs the exchanges: that is how a 1-GPU box tests them)
@@ -817,7 +830,7 @@ public:
     std::vector<uint32_t> anchor_flags_h;
     static constexpr int kAgain = -6; // PM_EAGAIN: the resident route does not apply; the caller takes the host route
 
-    void begin_store_call() { timing.clear(); last_events = last_rest = last_positions = last_candidates = last_accepted = last_grouped = 0; last_alg[0] = last_alg[1] = last_alg[2] = 0; }      // (counts of the last search travel with pm_last_timing)
+    void begin_store_call() { timing.clear(); last_events = last_rest = last_positions = last_candidates = last_accepted = last_grouped = last_grouped_wide = last_wide_regions = 0; last_handed_back = -1; last_alg[0] = last_alg[1] = last_alg[2] = 0; }      // (counts of the last search travel with pm_last_timing)
     Store store_view() { return Store{d_anchor_start.p, d_ms_strand.p, d_anchor_lon.p, d_anchor_flags.p, d_ms_shift.p, d_ms_len.p, d_ms_state.p, ngen}; }
     // coherent: the reader must see marks made while its kernel runs (a wavefront that validates candidates in order)
     Layout layout_view(uint64_t* image, bool coherent = true) { return Layout{image, d_lay_off.p, d_lay_bits.p, coherent ? 1 : 0}; }
@@ -1516,7 +1529,9 @@ public:
     int64_t tail_repeats = 0;     // tails repeated the exact way (a capacity too small, an anchor list that turned out short)
     bool tangle_rounds = true;    // tangled rows settled in rounds (TangleOwner / TangleSettle) before the one wavefront that takes what is left; false: that wavefront takes them all (tests)
     bool group_small = true;      // the events of a recursion batch's small regions once per distinct piece (GroupedPairEvents)
+    bool group_wide = false;      // ... and the small regions that form leaves (more pieces, more events, more genomes) by its wide form (GroupedPairEventsWide); off unless asked for: measured slower than pair by pair on every workload of DESIGN.md 8
     int64_t last_grouped = 0;
+    int64_t last_grouped_wide = 0, last_handed_back = -1, last_wide_regions = 0;      // of last_grouped, the wide form's events; small regions neither form took (-1: not counted); regions the wide form took
     bool force_atomic_marks = false;      // (tests) store_settle marks with atomic ORs although the list is in order
     int filter_factor = 8;                // presence-filter bits per reference position, before rounding up to a power of two
     int slot_factor = 2;                  // index slots per reference position, before rounding up to a power of two (a measurement switch)
@@ -1548,6 +1563,7 @@ public:
         if (key == "order_debug") { order_debug = value != 0; return true; }
         if (key == "timing") { phase_timing = value != 0; be.timing_on = phase_timing; return true; }
         if (key == "group_small") { group_small = value != 0; return true; }
+        if (key == "group_wide") { group_wide = value != 0; return true; }
         if (key == "work_budget" && value > 0) { work_budget = value; return true; }
         if (key == "dense_all") { dense_all = value != 0; return true; }
         if (key == "dirty_min" && value >= 0) { dirty_min = value; return true; }

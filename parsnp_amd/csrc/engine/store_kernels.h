@@ -963,6 +963,240 @@ struct GroupedBounds {
     PM_HD void operator()(int64_t pair) const { if (flag[pair / nq]) lo[pair] = glo[pair]; }
 };
 
+// The WIDE form of GroupedPairEvents: the small regions the first form leaves -- more than kGrpPieces distinct pieces (a divergent
+// or rearranged set), more than kGrpEvents events of one (piece, strand), or a batch of more than kGrpGenomes query genomes --
+// up to kWidePieces pieces, kWideEvents events and kWideGenomes genomes.  The same three steps, the same outputs in the same
+// layout (glo, flag, the keys and values, the EventAtK states, emax, epm), the same block counter; a region beyond these limits,
+// or with a side above 128 bases, keeps flag 0 and nothing of it is written: SmallPairEvents takes it.
+// What differs, so that the tables stay at 46 KB of LDS per wavefront (three wavefronts to a CU) instead of 76 KB:
+//   - the state lists (sh_st of the first form, as large as the event lists) do not exist.  An event word carries rep' of its
+//     reference position in its top byte (an emitted event has rep' < len <= 128), and the lane that copies a genome's events
+//     folds the running state of both strands as it merges them -- the same fold, once per genome instead of once per piece;
+//   - events of equal reference position are ordered by their query position, so the block is the same bytes in every run.
+// Built so that it cannot wait for anything: every loop has a constant trip count, or a wave-uniform one with a constant bound
+// (the rounds over the genomes of a lane, at most kWideGenomes / 64 + 1; the election, at most 65 rounds a time and
+// kWidePieces + 1 elections in all), or -- inside a lanes_for body, where nothing crosses lanes -- a count of the lane's own
+// with a constant bound.  wave_sync and the lds atomics stand where all 64 lanes arrive alike: what the lanes branch on around
+// them (sh_elect, sh_bad, npieces, flag[r]) is one word that every lane reads after a wave_sync.  No lane reads memory twice to
+// see it change.
+constexpr int kWideEvents = 32;
+constexpr int kWidePieces = 128;
+constexpr int kWideGenomes = 2047;      // (a piece number fits a byte; the numbers of one region's genomes sit in LDS)
+struct GroupedPairEventsWide {
+    Packed P; const RegionInfo* R; const int64_t* starts; const int64_t* lens; int32_t ngen; const int32_t* rep;
+    uint64_t* ev_key; uint64_t* ev_val; uint64_t* block_count; uint64_t ev_cap; int lbits; int64_t* glo; int32_t g_first, g_last;
+    uint8_t* flag;      // [region]: as GroupedPairEvents leaves it
+    EventAtK* st; int32_t* emax; int32_t* epm;
+    int64_t nreg;       // the launch is xcd_grid(nreg) wavefronts
+    int after_first;    // != 0: GroupedPairEvents ran before this launch: flag[r] is written, and a region with flag 1 is done
+    uint64_t* wide;     // [0] += events written here, [1] += small regions handed back, [2] += regions taken here
+    PM_HD void wave(int64_t w) const {
+        const int64_t r = xcd_item(w, nreg);
+        if (r >= nreg) return;
+        if (after_first && flag[r]) return;
+        const int32_t nq = ngen - 1;
+        const int per = (nq + 63) / 64;      // (at most kWideGenomes / 64 + 1 = 32: the caller launches this form up to kWideGenomes)
+        const RegionInfo& ri = R[r];
+        const int32_t nR = ri.nR, L = ri.minlen;
+        const int64_t rbase = P.goff[0] + ri.ref_pos;
+        uint32_t big = nR > 128 || nq > kWideGenomes ? 1u : 0u;
+        lanes_for(1, ngen, [&](int g) { if (lens[r * ngen + g] > 128) big = 1; });
+        big = wave_or_u32(big);
+        if (big) { if (wave_leader()) flag[r] = 0; return; }
+        PM_WAVE_SHARED uint64_t sh_pl[64][6];           // the lanes' pieces of the running round
+        PM_WAVE_SHARED int32_t sh_m[64];                // ... their lengths (-1: no genome)
+        PM_WAVE_SHARED uint8_t sh_open[64];             // ... not numbered yet
+        PM_WAVE_SHARED uint64_t rp_pl[kWidePieces][6];  // the distinct pieces
+        PM_WAVE_SHARED int32_t rp_m[kWidePieces];
+        PM_WAVE_SHARED int32_t rp_g[kWidePieces];       // a genome that holds the piece
+        PM_WAVE_SHARED uint8_t sh_piece[kWideGenomes + 1];      // genome -> number of its piece
+        PM_WAVE_SHARED uint32_t sh_ev[2 * kWidePieces][kWideEvents];      // l | j << 8 | len << 16 | rep'[l] << 24
+        PM_WAVE_SHARED int32_t sh_cnt[2 * kWidePieces];
+        PM_WAVE_SHARED uint8_t sh_used[kWidePieces];    // a genome of this rank holds the piece
+        PM_WAVE_SHARED int32_t sh_tot[64];
+        PM_WAVE_SHARED int32_t sh_elect;
+        PM_WAVE_SHARED int32_t sh_bad;
+        PM_WAVE_SHARED uint64_t sh_base;
+        if (wave_leader()) sh_bad = 0;
+        lanes_for(0, kWidePieces, [&](int i) { sh_used[i] = 0; });
+        int npieces = 0;      // (the same in every lane: it follows sh_elect)
+        bool bad = false;     // (... and so is this: sh_bad after a wave_sync)
+        // 1. number the pieces
+        for (int k = 0; k < per && !bad; k++) {
+            wave_sync();
+            lanes_for(0, 64, [&](int t) {
+                const int g = 1 + t * per + k;
+                int32_t m = -1;
+                if (g < ngen) {
+                    m = (int32_t)lens[r * ngen + g];
+                    const int64_t qpos = P.goff[2 * g] + starts[r * ngen + g];
+                    const W128 v = W128::ones(m);
+                    for (int pl = 0; pl < 3; pl++) { const W128 x = W128::load(P.blk, qpos, pl) & v; sh_pl[t][2 * pl] = x.lo; sh_pl[t][2 * pl + 1] = x.hi; }
+                }
+                sh_m[t] = m;
+                uint8_t open = m >= 0;
+                for (int i = 0; i < kWidePieces; i++) {
+                    if (i >= npieces || !open) break;
+                    if (rp_m[i] != m) continue;
+                    bool same = true;
+                    for (int x = 0; x < 6; x++) same = same && rp_pl[i][x] == sh_pl[t][x];
+                    if (same) { sh_piece[g - 1] = (uint8_t)i; open = 0; }
+                }
+                sh_open[t] = open;
+            });
+            for (int round = 0; round < 65; round++) {      // the lowest lane with a piece that is not in the table adds its own: at most 64 of them, and the round that finds none
+                wave_sync();
+                if (wave_leader()) sh_elect = 64;
+                wave_sync();
+                lanes_for(0, 64, [&](int t) { if (sh_open[t]) lds_min32(&sh_elect, t); });
+                wave_sync();
+                const int e = sh_elect;
+                if (e == 64) break;
+                if (npieces == kWidePieces) { if (wave_leader()) sh_bad = 1; break; }      // (the election that would be number kWidePieces + 1)
+                lanes_for(0, 64, [&](int t) {
+                    if (t != e) return;
+                    for (int x = 0; x < 6; x++) rp_pl[npieces][x] = sh_pl[t][x];
+                    rp_m[npieces] = sh_m[t]; rp_g[npieces] = 1 + t * per + k;
+                });
+                wave_sync();
+                lanes_for(0, 64, [&](int t) {
+                    if (!sh_open[t] || rp_m[npieces] != sh_m[t]) return;
+                    bool same = true;
+                    for (int x = 0; x < 6; x++) same = same && rp_pl[npieces][x] == sh_pl[t][x];
+                    if (same) { sh_piece[t * per + k] = (uint8_t)npieces; sh_open[t] = 0; }
+                });
+                npieces++;
+            }
+            wave_sync();
+            bad = sh_bad != 0;
+        }
+        // 2. the events of every (piece, strand): the lanes take the tasks in turn and, where there are fewer tasks than lanes, split a task's diagonals
+        const int tasks = 2 * npieces;      // (2 ... 2 kWidePieces: a region has a query genome)
+        int share = 1;
+        for (int x = 0; x < 5; x++) if (share * 2 * tasks <= 64) share *= 2;      // lanes per task
+        if (!bad) {
+            lanes_for(0, tasks, [&](int wi) { sh_cnt[wi] = 0; });
+            wave_sync();
+            lanes_for(0, tasks * share, [&](int t) {
+                const int wi = t / share, sub = t % share;
+                const int g = rp_g[wi >> 1], strand = wi & 1;
+                const int32_t m = rp_m[wi >> 1];
+                if (m < L || nR < L) return;
+                const int64_t qs = starts[r * ngen + g];
+                const int64_t qbase = strand ? P.goff[2 * g + 1] + (P.glen[g] - qs - m) : P.goff[2 * g] + qs;
+                auto emit = [&](int32_t l0, int32_t j0, int32_t len) {
+                    const int32_t rp = rep[ri.posbase + l0];
+                    if (len <= rp) return;             // not unique in R
+                    const int32_t at = lds_add32(&sh_cnt[wi], 1);
+                    if (at < kWideEvents) sh_ev[wi][at] = (uint32_t)l0 | ((uint32_t)j0 << 8) | ((uint32_t)len << 16) | ((uint32_t)(rp & 0xff) << 24);
+                    if (rp < 0) sh_bad = 1;            // (never: rep' is a length)
+                };
+                if (nR <= 64 && m <= 64) pair_diagonals<W64>(P, rbase, qbase, nR, m, L, emit, sub, share);
+                else pair_diagonals<W128>(P, rbase, qbase, nR, m, L, emit, sub, share);
+            });
+            wave_sync();
+            lanes_for(0, tasks, [&](int wi) {      // in order of the reference position, then of the query position (at most kWideEvents entries: by insertion)
+                const int n = sh_cnt[wi];
+                if (n > kWideEvents) { sh_bad = 1; return; }
+                for (int i = 1; i < kWideEvents; i++) {
+                    if (i >= n) break;
+                    const uint32_t e = sh_ev[wi][i];
+                    const uint32_t key = ((e & 0xffu) << 8) | ((e >> 8) & 0xffu);      // (l, j)
+                    int at = i;
+                    for (int x = 0; x < kWideEvents; x++) {
+                        if (at == 0 || (((sh_ev[wi][at - 1] & 0xffu) << 8) | ((sh_ev[wi][at - 1] >> 8) & 0xffu)) <= key) break;
+                        sh_ev[wi][at] = sh_ev[wi][at - 1]; at--;
+                    }
+                    sh_ev[wi][at] = e;
+                }
+            });
+        }
+        wave_sync();
+        if (sh_bad) {      // SmallPairEvents takes the region
+            if (wave_leader()) { flag[r] = 0; atomic_add64(wide + 1, 1); }
+            return;
+        }
+        // 3. the block: every lane's share, then the events of its genomes
+        lanes_for(0, 64, [&](int t) {
+            int c = 0;
+            for (int k = 0; k < per; k++) {
+                const int g = 1 + t * per + k;
+                if (g < ngen && g >= g_first && g < g_last) { const int i = sh_piece[g - 1]; c += sh_cnt[2 * i] + sh_cnt[2 * i + 1]; sh_used[i] = 1; }
+            }
+            sh_tot[t] = c;
+        });
+        wave_sync();
+        // Master.EP of the region, as in the first form: a piece's EP at k = the furthest end over its events that start at or before k
+        lanes_for(0, nR, [&](int k) {
+            int32_t ep = nR;
+            for (int i = 0; i < kWidePieces; i++) {
+                if (i >= npieces) break;
+                if (!sh_used[i]) continue;
+                int32_t v = 0;
+                for (int sd = 0; sd < 2; sd++) {
+                    const int wi = 2 * i + sd, n = sh_cnt[wi];
+                    for (int x = 0; x < kWideEvents; x++) {
+                        if (x >= n) break;
+                        const uint32_t e = sh_ev[wi][x];
+                        if ((int32_t)(e & 0xffu) > k) break;
+                        const int32_t end = (int32_t)(e & 0xffu) + (int32_t)((e >> 16) & 0xffu);
+                        if (end > v) v = end;
+                    }
+                }
+                if (v < ep) ep = v;
+            }
+            epm[ri.posbase + k] = ep;
+        });
+        if (wave_leader()) {
+            int total = 0;
+            for (int t = 0; t < 64; t++) { const int c = sh_tot[t]; sh_tot[t] = total; total += c; }
+            sh_base = total ? atomic_add64(block_count, (uint64_t)total) : 0;
+            flag[r] = 1;
+            if (total) atomic_add64(wide, (uint64_t)total);
+            atomic_add64(wide + 2, 1);
+        }
+        wave_sync();
+        lanes_for(0, 64, [&](int t) {
+            uint64_t at0 = sh_base + (uint64_t)sh_tot[t];
+            for (int k = 0; k < per; k++) {
+                const int g = 1 + t * per + k;
+                if (g >= ngen) break;
+                const int64_t pair = r * nq + (g - 1);
+                glo[pair] = (int64_t)at0;
+                if (g < g_first || g >= g_last) continue;
+                const int i = sh_piece[g - 1];
+                const uint32_t* a = sh_ev[2 * i]; const uint32_t* b = sh_ev[2 * i + 1];
+                const int na = sh_cnt[2 * i], nb = sh_cnt[2 * i + 1], c = na + nb;
+                if (at0 + (uint64_t)c <= ev_cap) {
+                    // the running state of both strands, as win_join keeps it and WaveScan resolves it (GroupedPairEvents, 2b)
+                    struct Run { int32_t e1, e2, wl, wj, up; bool have; } f{0, 0, 0, 0, 0, false}, v{0, 0, 0, 0, 0, false};
+                    auto fold = [](Run& q, int32_t l, int32_t j, int32_t end, int32_t rp) {
+                        const bool take = !q.have || end > q.e1 || (end == q.e1 && (l < q.wl || (l == q.wl && j < q.wj)));
+                        if (take) { if (q.have && q.e1 > q.e2) q.e2 = q.e1; q.e1 = end; q.wl = l; q.wj = j; q.up = l + rp; q.have = true; }
+                        else if (end > q.e2) q.e2 = end;
+                    };
+                    int ia = 0, ib = 0;
+                    for (int x = 0; x < 2 * kWideEvents; x++) {      // merged by (reference position, strand): the order of the sort key
+                        if (x >= c) break;
+                        const bool fwd = ib >= nb || (ia < na && (a[ia] & 0xffu) <= (b[ib] & 0xffu));
+                        const uint32_t e = fwd ? a[ia++] : b[ib++];
+                        const int32_t l = (int32_t)(e & 0xffu), j = (int32_t)((e >> 8) & 0xffu), len = (int32_t)((e >> 16) & 0xffu);
+                        if (fwd) fold(f, l, j, l + len, (int32_t)(e >> 24)); else fold(v, l, j, l + len, (int32_t)(e >> 24));
+                        ev_key[at0 + x] = ((((uint64_t)pair << lbits) | (uint64_t)l) << 1) | (fwd ? 0ull : 1ull);
+                        ev_val[at0 + x] = ((uint64_t)j << 32) | (uint64_t)len;
+                        EventAtK o;
+                        o.s[0] = f.have ? StrandAtK{f.e1, f.e2 > f.up ? f.e2 : f.up, f.wj - f.wl} : StrandAtK{0, 0, 0};
+                        o.s[1] = v.have ? StrandAtK{v.e1, v.e2 > v.up ? v.e2 : v.up, v.wj - v.wl} : StrandAtK{0, 0, 0};
+                        st[at0 + x] = o;
+                        emax[at0 + x] = o.s[0].e1 > o.s[1].e1 ? o.s[0].e1 : o.s[1].e1;
+                    }
+                }
+                at0 += (uint64_t)c;
+            }
+        });
+    }
+};
+
 // ------------------------------------------------------------------------------------------ one generation of the recursion
 // doWork (src/parsnp.cpp:173-317) pops the region with the smallest reference start, validates its candidates in order
 // (setMums1, second half), pushes the neighbour regions of every new MUM that are longer than q (:215-254) and sorts.  The

@@ -373,6 +373,10 @@ void Aligner::collect_engine_timing() {
         if (!strcmp(names[i], "alg_survey")) { stats.alg_bytes += ms[i]; continue; }
         if (!strcmp(names[i], "alg_kernel")) { stats.alg_bytes_kernel += ms[i]; continue; }
         if (!strcmp(names[i], "alg_query")) { stats.alg_bytes_query += ms[i]; continue; }
+        // (... and what the wide grouped form did: kept out of the phase tables, whose readers know their counts by name)
+        if (!strcmp(names[i], "n_grouped_wide")) { stats.grouped_wide += ms[i]; continue; }
+        if (!strcmp(names[i], "n_wide_regions")) { stats.wide_regions += ms[i]; continue; }
+        if (!strcmp(names[i], "n_handed_back")) { if (ms[i] > 0) stats.handed_back += ms[i]; continue; }
         if (timing_first_call_) stats.anchor_ms.emplace_back(names[i], ms[i]);
         bool merged = false;
         for (auto& kv : stats.engine_ms) if (kv.first == names[i]) { kv.second += ms[i]; merged = true; }

@@ -117,6 +117,7 @@ int CoreRun::open(const std::string& ini_path) {
     if (const char* v = test_hook("PM_TANGLED_MAX")) (void)pm_session_tune(session, "tangled_max", atol(v));
     if (const char* v = test_hook("PM_ATOMIC_MARKS")) (void)pm_session_tune(session, "atomic_marks", atol(v));
     if (const char* v = test_hook("PM_GROUP_SMALL")) (void)pm_session_tune(session, "group_small", atol(v));
+    if (const char* v = test_hook("PM_GROUP_WIDE")) (void)pm_session_tune(session, "group_wide", atol(v));
     if (const char* v = test_hook("PM_MASTER_SEG")) (void)pm_session_tune(session, "master_seg", atol(v));
     if (const char* v = test_hook("PM_STAGE_GATE")) (void)pm_session_tune(session, "stage_gate", atol(v));
     if (const char* v = test_hook("PM_CLUSTER_UNSURE")) (void)pm_session_tune(session, "cluster_unsure", atol(v));
