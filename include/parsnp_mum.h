@@ -173,6 +173,8 @@ int64_t pm_result_table_id(const pm_result* r);
  *                  the exact test -- extents ORed into a scratch image -- must find them disjoint and the same bytes result)
  *   "order_debug"  != 0: the order check (pm_store_order_check / pm_store_chain_begin) waits for its kernels and prints to stderr
  *                  how many candidates it had noted and how many its bounds left to the scan
+ *   "chain_window" 1 .. 65 536 (4 096): the passed MUMs in a row that pm_store_chain_begin follows with diag_diff > 1; a longer
+ *                  run is reported in bit 3 of pm_chain_info.trouble (tests set it low)
  *   "chain_tie"    != 0: pm_store_chain_begin reports two MUMs with one reference start although there is none (tests: the
  *                  caller's own list logic must give the same bytes)
  *   "timing"       0: no HIP events around the phases of a call (pm_last_timing then reports counts only)
@@ -282,21 +284,29 @@ int pm_store_fill(pm_session* s, const int32_t* last_of, const int32_t* first_of
 const int64_t* pm_store_fill_starts(const pm_session* s);
 const int64_t* pm_store_fill_ends(const pm_session* s);
 /* Phases C-D in one queue of launches, for a run whose list logic is order-free -- all reference starts of the accepted MUMs
- * differ, diag_diff <= 1 (the ratio test joins or closes, :2693), no MUM short enough for filterRandom1 (:338-425): the sort by
- * reference start (:338, :2571), the chain walk of setFinalClusters (:2563-2719; the pairwise test of pm_store_judge, pairs with
- * reverse-strand members included, with the ratio test applied on the device in the reference's float / double mix), the
- * dissolving of LCBs no longer than c by filterRandomClustersSimple1 (:433-497; the last LCB is never examined, :447; their
- * MUMs leave the layout), the second chaining pass (:3261-3268) and the fillers of setInterClusterRegions (:2389-2460; counted:
- * a filler is never printed, it shifts the numbers of the LCBs behind it).  _begin queues the work and returns; _end waits
- * for it: n_mums store rows in reference order (rows), a flag per MUM that begins an LCB (heads) -- both valid until the
- * session's next chain call -- and the counters of the log.  trouble != 0: bit 0 two MUMs share a reference start (the
- * reference's unstable sort decides: nothing on the device has changed, the caller runs pm_store_judge / _unmark / _fill with
- * its own list logic); bit 1 the reference's filler bookkeeping would overrun (:2419-2433, pm_store_fill's add = 2); bit 2 the
- * order check (pm_store_order_check) failed: nothing has changed, the caller discards the run and takes the host route.
- * n_expected: the number of accepted store rows (the caller's MUM list); a mismatch is an error. */
+ * differ, no MUM short enough for filterRandom1 (:338-425): the sort by reference start (:338, :2571), the chain walk of
+ * setFinalClusters (:2563-2719; the pairwise test of pm_store_judge, pairs with reverse-strand members included, with the test
+ * of :2684-2700 applied on the device in the reference's float / double mix), the dissolving of LCBs no longer than c by
+ * filterRandomClustersSimple1 (:433-497; the last LCB is never examined, :447; their MUMs leave the layout), the second
+ * chaining pass (:3261-3268) and the fillers of setInterClusterRegions (:2389-2460; counted: a filler is never printed, it
+ * shifts the numbers of the LCBs behind it).  diag_diff <= 1 is a ratio (a MUM joins the open chain or closes it, :2693);
+ * diag_diff > 1 is a difference in bases (:2684-2692): a MUM whose gaps differ by that much or more is PASSED -- neither joined
+ * nor closing; the next MUM is judged against the chain's last joined MUM -- stays in the list in no LCB, and is judged again
+ * in the second pass.  _begin queues the work and returns; _end waits for it: n_mums store rows in reference order (rows), a
+ * byte per MUM (heads: 0 a member of the LCB open at it, 1 it begins an LCB, 2 it is in no LCB; 2 only with diag_diff > 1) --
+ * both valid until the session's next chain call -- and the counters of the log.  trouble != 0: bit 0 two MUMs share a
+ * reference start (the reference's unstable sort decides: nothing on the device has changed, the caller runs pm_store_judge /
+ * _unmark / _fill with its own list logic); bit 1 the reference's filler bookkeeping would overrun (:2419-2433, pm_store_fill's
+ * add = 2); bit 2 the order check (pm_store_order_check) failed: nothing has changed, the caller discards the run and takes
+ * the host route; bit 3 (diag_diff > 1) more passed MUMs in a row than "chain_window" (pm_session_tune), or more than 65 536
+ * places where a run of them may begin: nothing has changed, the caller runs its own list logic as for bit 0.
+ * n_expected: the number of accepted store rows (the caller's MUM list); a mismatch is an error.
+ * pm_store_chain_passed: the number of MUMs in no LCB after the first and after the second chaining pass of the last
+ * pm_store_chain_end (PM_EINVAL before the first one). */
 typedef struct { int64_t n_in, lcbs_first, lcbs_dissolved, mums_dissolved, n_mums, n_lcbs, n_fillers; uint64_t trouble; } pm_chain_info;
 int pm_store_chain_begin(pm_session* s, int64_t n_expected, int32_t d, float diag_diff, int64_t c);
 int pm_store_chain_end(pm_session* s, pm_chain_info* info, const int32_t** rows, const uint8_t** heads);
+int pm_store_chain_passed(const pm_session* s, int64_t* first_pass, int64_t* second_pass);
 /* Rows for the host (the XMFA writer after the LCBs are final; a caller falling back to the host route): start[i * n_genomes + j]
  * with the trim applied (raw != 0: as the search delivered it), strand byte.  rows == NULL: store rows [first, first + n). */
 int pm_store_rows(pm_session* s, const int32_t* rows, int64_t first, int64_t n, int raw, int32_t* start, uint8_t* strand);

@@ -135,6 +135,16 @@ class Session:
         self.lib.L.pm_session_tune.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
         self.lib._check(self.lib.L.pm_session_tune(self.h, key.encode(), value))
 
+    def chain_passed(self):
+        """pm_store_chain_passed: MUMs in no LCB after the first and the second chaining pass of the last pm_store_chain_end (a
+        diagonal difference in bases: pm_store_chain_begin with diag_diff > 1)"""
+        if not hasattr(self.lib.L, "pm_store_chain_passed"):
+            raise PmError("this provider of the ABI has no pm_store_chain_passed")
+        a, b = C.c_int64(), C.c_int64()
+        self.lib.L.pm_store_chain_passed.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        self.lib._check(self.lib.L.pm_store_chain_passed(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def __enter__(self):
         return self
 

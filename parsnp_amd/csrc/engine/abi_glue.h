@@ -236,6 +236,12 @@ int pm_store_chain_end(pm_session* s, pm_chain_info* info, const int32_t** rows,
     static_assert(sizeof(pm_chain_info) == sizeof(pm::Engine<PmBackend>::ChainInfo), "pm_chain_info");
     PM_STORE_CALL(s->engine->store_chain_end((pm::Engine<PmBackend>::ChainInfo*)info, rows, heads))
 }
+int pm_store_chain_passed(const pm_session* s, int64_t* first_pass, int64_t* second_pass) {
+    if (!s || !first_pass || !second_pass) return fail(PM_EINVAL, "bad argument");
+    if (s->engine->chain_passed[0] < 0) return fail(PM_EINVAL, "no chain call has ended");
+    *first_pass = s->engine->chain_passed[0]; *second_pass = s->engine->chain_passed[1];
+    return PM_OK;
+}
 const int64_t* pm_store_fill_starts(const pm_session* s) { return s ? s->fill_starts.data() : nullptr; }
 const int64_t* pm_store_fill_ends(const pm_session* s) { return s ? s->fill_ends.data() : nullptr; }
 int pm_store_rows(pm_session* s, const int32_t* rows, int64_t first, int64_t n, int raw, int32_t* start, uint8_t* strand) {

@@ -1378,24 +1378,46 @@ public:
         const int64_t* n1 = d_ch_pos.p + rows;
         int64_t* hdr = d_ch_hdr.p;
         uint64_t* trouble = (uint64_t*)(hdr + kChTrouble);
+        // diag_diff in bases: a MUM may be passed, so the verdicts against the list predecessor are followed by the windows (store_kernels.h,
+        // "phases C-D on the store"), and a dissolved MUM leaves the layout only when the windows of BOTH passes had nothing to report
+        const bool bp = diag_diff > 1.0f;
+        int64_t* back = nullptr;
+        if (bp) {
+            ensure(d_ch_back, cap); ensure(d_ch_wflag, cap + 1); ensure(d_ch_wpos, cap + 1); ensure(d_ch_wend, cap); ensure(d_ch_wverdict, cap);
+            ensure(d_ch_wlist, (size_t)kChainStarts); ensure(d_ch_wkeep, (size_t)kChainStarts);
+            back = d_ch_back.p;
+        }
+        const int64_t nstarts = std::min<int64_t>((int64_t)cap, kChainStarts);
+        auto windows = [&](const uint64_t* row, const int64_t* n) {
+            be.launch("chain_starts", (int64_t)cap + 1, ChainHeads{d_ch_verdict.p, n, d_ch_wflag.p, kChPass});
+            be.exclusive_scan(d_ch_wflag.p, d_ch_wpos.p, cap + 1);
+            be.launch_wave("chain_window", (int64_t)cap, ChainWindow{S, row, n, d, diag_diff, d_ch_verdict.p, chain_window, d_ch_wpos.p, d_ch_wlist.p, d_ch_wend.p, d_ch_wverdict.p});
+            be.launch("chain_select", 1, ChainSelect{n, d_ch_wpos.p, d_ch_wlist.p, d_ch_wend.p, d_ch_wkeep.p, trouble});
+            be.launch_wave("chain_window_fill", nstarts, ChainWindowFill{n, d_ch_wpos.p, d_ch_wlist.p, d_ch_wend.p, d_ch_wverdict.p, d_ch_wkeep.p, trouble, d_ch_verdict.p, back});
+        };
         // first pass: verdicts, chains, their lengths, the dissolved ones out of the layout and out of the list
-        be.launch_wave("chain_judge", (int64_t)cap, ChainJudge{S, d_ch_skey.p, d_ch_srow.p, n1, d, diag_diff, d_ch_verdict.p, trouble, force_chain_tie ? 1 : 0});
+        be.launch_wave("chain_judge", (int64_t)cap, ChainJudge{S, d_ch_skey.p, d_ch_srow.p, n1, d, diag_diff, d_ch_verdict.p, trouble, force_chain_tie ? 1 : 0, back});
         be.launch("chain_judge_reverse", (int64_t)cap, ChainJudgeReverse{S, d_ch_srow.p, n1, d, diag_diff, d_ch_verdict.p});
-        be.launch("chain_heads", (int64_t)cap + 1, ChainHeads{d_ch_verdict.p, n1, d_ch_head.p});
+        if (bp) windows(d_ch_srow.p, n1);
+        be.launch("chain_heads", (int64_t)cap + 1, ChainHeads{d_ch_verdict.p, n1, d_ch_head.p, kChClose});
         be.exclusive_scan(d_ch_head.p, d_ch_hpos.p, cap + 1);
-        be.launch("chain_lcb_sum", (int64_t)cap, ChainLcbSum{S, d_ch_srow.p, n1, d_ch_hpos.p, d_ch_lcblen.p});
-        be.launch("chain_dissolve", (int64_t)cap + 1, ChainDissolve{n1, d_ch_hpos.p, d_ch_head.p, d_ch_lcblen.p, c, d_ch_survive.p, hdr});
-        be.launch_wave("chain_unmark", (int64_t)cap, ChainUnmark{S, layout_view(d_image.p), d_ch_srow.p, n1, d_ch_survive.p});
+        be.launch("chain_lcb_sum", (int64_t)cap, ChainLcbSum{S, d_ch_srow.p, n1, d_ch_hpos.p, d_ch_verdict.p, d_ch_lcblen.p, hdr});
+        be.launch("chain_dissolve", (int64_t)cap + 1, ChainDissolve{n1, d_ch_hpos.p, d_ch_head.p, d_ch_verdict.p, d_ch_lcblen.p, c, d_ch_survive.p, hdr});
+        if (!bp) be.launch_wave("chain_unmark", (int64_t)cap, ChainUnmark{S, layout_view(d_image.p), d_ch_srow.p, n1, d_ch_survive.p, nullptr});
         be.exclusive_scan(d_ch_survive.p, d_ch_spos.p, cap + 1);
         be.launch("chain_compact", (int64_t)cap, ChainCompact{n1, d_ch_survive.p, d_ch_spos.p, d_ch_skey.p, d_ch_srow.p, d_ch_key2.p, d_ch_row2.p, hdr});
         // second pass (the reference chains again after dissolving, :3261-3268), then the fillers between the final LCBs
         const int64_t* n2 = hdr + kChN2;
-        be.launch_wave("chain_judge", (int64_t)cap, ChainJudge{S, d_ch_key2.p, d_ch_row2.p, n2, d, diag_diff, d_ch_verdict.p, trouble, 0});
+        be.launch_wave("chain_judge", (int64_t)cap, ChainJudge{S, d_ch_key2.p, d_ch_row2.p, n2, d, diag_diff, d_ch_verdict.p, trouble, 0, back});
         be.launch("chain_judge_reverse", (int64_t)cap, ChainJudgeReverse{S, d_ch_row2.p, n2, d, diag_diff, d_ch_verdict.p});
-        be.launch("chain_heads", (int64_t)cap + 1, ChainHeads{d_ch_verdict.p, n2, d_ch_head.p});
+        if (bp) {
+            windows(d_ch_row2.p, n2);
+            be.launch_wave("chain_unmark", (int64_t)cap, ChainUnmark{S, layout_view(d_image.p), d_ch_srow.p, n1, d_ch_survive.p, trouble});
+        }
+        be.launch("chain_heads", (int64_t)cap + 1, ChainHeads{d_ch_verdict.p, n2, d_ch_head.p, kChClose});
         be.exclusive_scan(d_ch_head.p, d_ch_hpos.p, cap + 1);
-        if (cap > 1) be.launch_wave("chain_fill", (int64_t)cap - 1, ChainFill{S, layout_view(d_image.p, false), P, d_ch_row2.p, n2, d_ch_head.p, hdr});
-        be.launch("chain_out", (int64_t)cap, ChainOut{d_ch_row2.p, n2, d_ch_head.p, d_ch_hpos.p, d_ch_outrow.p, d_ch_outhead.p, hdr});
+        if (cap > 1) be.launch_wave("chain_fill", (int64_t)cap - 1, ChainFill{S, layout_view(d_image.p, false), P, d_ch_row2.p, n2, d_ch_head.p, back, hdr});
+        be.launch("chain_out", (int64_t)cap, ChainOut{d_ch_row2.p, n2, d_ch_head.p, d_ch_hpos.p, d_ch_verdict.p, d_ch_outrow.p, d_ch_outhead.p, hdr});
         be.mark(nullptr);
         be.d2h_async_pinned(chain_host, hdr, 8 * (size_t)kChWords);
         be.d2h_async_pinned(chain_host + 8 * (size_t)kChWords, d_ch_outrow.p, 4 * cap);
@@ -1414,6 +1436,7 @@ public:
         *rows = (const int32_t*)(chain_host + 8 * (size_t)kChWords);
         *heads = chain_host + 8 * (size_t)kChWords + 4 * (size_t)chain_cap;
         collect_timing_more();
+        chain_passed[0] = h[kChPass1]; chain_passed[1] = h[kChPass2];
         if (info->n_in != chain_cap) { error = "the MUM list of the caller and the accepted rows of the store differ"; return -2; }
         return 0;
     }
@@ -1538,6 +1561,8 @@ public:
     bool bucket_sort = true;              // the events put in order by (pair, 256-position block) buckets (EventBucketCount ... CoarseFromBuckets); false: gathered and radix-sorted
     bool master_seg = true;               // Master.EP from the genomes' segments (MasterEPSeg); false: every lane against every staged event (MasterEP)
     bool force_gate = false;              // (tests) the second stage of a two-stage store_validate never runs
+    int64_t chain_window = 4096;          // passed MUMs in a row that a window of store_chain_begin walks (diag_diff in bases); more: kChainWindow, the caller's list logic
+    int64_t chain_passed[2] = {-1, -1};   // MUMs in no LCB after the first / the second chaining pass of the last store_chain_end (-1: none yet)
     bool force_chain_tie = false;         // (tests) store_chain_begin reports two MUMs with one reference start
     bool force_unsure = false;            // (tests) store_validate's collinear test of the clusters reports failure: the exact test decides
     bool order_debug = false;             // the order check prints its counts (noted candidates, candidates left to the scan) to stderr
@@ -1558,6 +1583,7 @@ public:
         if (key == "filter_factor") { filter_factor = value < 1 ? 1 : (int)value; return true; }
         if (key == "slot_factor") { slot_factor = value < 1 ? 1 : (int)value; return true; }
         if (key == "stage_gate") { force_gate = value != 0; return true; }
+        if (key == "chain_window" && value >= 1 && value <= kChainWindowMax) { chain_window = value; return true; }
         if (key == "chain_tie") { force_chain_tie = value != 0; return true; }
         if (key == "cluster_unsure") { force_unsure = value != 0; return true; }
         if (key == "order_debug") { order_debug = value != 0; return true; }
@@ -1673,6 +1699,7 @@ private:
     Buf<int64_t> d_ch_flag, d_ch_pos, d_ch_head, d_ch_hpos, d_ch_survive, d_ch_spos, d_ch_hdr;
     Buf<uint64_t> d_ch_key, d_ch_val, d_ch_skey, d_ch_srow, d_ch_key2, d_ch_row2, d_ch_lcblen;
     Buf<uint8_t> d_ch_verdict, d_ch_outhead; Buf<int32_t> d_ch_outrow;
+    Buf<int64_t> d_ch_back, d_ch_wflag, d_ch_wpos, d_ch_wlist, d_ch_wend; Buf<uint8_t> d_ch_wverdict, d_ch_wkeep;      // diag_diff in bases: the windows
     uint8_t* chain_host = nullptr; size_t chain_host_cap = 0; void* chain_event = nullptr; bool chain_pending = false; int64_t chain_cap = 0;
     size_t lay_words = 0, rg_cap_hint = 0;
     int64_t layout_rows = -1;       // >= 0: the image holds the layout of the current anchor table (store_settle ran)

@@ -1922,18 +1922,29 @@ struct FillBetween {
 // ------------------------------------------------------------------------------------------ phases C-D on the store
 // The list logic of filterRandom1's sort (:338), setFinalClusters (:2563-2719), filterRandomClustersSimple1 (:433-497), the second
 // setFinalClusters (:3261-3268) and setInterClusterRegions (:2389-2460) for the case in which it is ORDER-FREE: all reference
-// starts of the accepted MUMs differ (one sorted order; the unstable std::sort of the reference cannot show), the ratio test
-// has two outcomes (diag_diff <= 1: a MUM joins the open chain or closes it, so the chain's last MUM is always the list
-// predecessor and the chains are the maximal runs between "close" verdicts), every MUM is longer than the filter length.
-// Then the sorted list is a radix sort of (reference start, row), a chain boundary is a flag per consecutive pair, an LCB's
-// length a segmented sum, the dissolved LCBs (length <= c, never the last: :447) a flag per LCB, the second chaining pass the
-// same flags over the compacted list, and the fillers a test per consecutive pair of final LCBs.  The host receives the
-// sorted rows of the final MUM list, a head flag per MUM and seven counters; what is not order-free (a tie) is reported in the
-// trouble word and the caller runs its own list logic instead -- nothing on the device has changed by then.
-constexpr uint8_t kChJoin = 0, kChClose = 1;
-constexpr uint64_t kChainTie = 1, kChainOverrun = 2, kChainOrder = 4;      // (kChainOrder: the order check, ForeignBound and the kernels around it, queued ahead of the chain kernels)
+// starts of the accepted MUMs differ (one sorted order; the unstable std::sort of the reference cannot show) and every MUM is
+// longer than the filter length.  Then the sorted list is a radix sort of (reference start, row), an LCB's length a segmented
+// sum, the dissolved LCBs (length <= c, never the last: :447) a flag per LCB, the second chaining pass the same kernels over the
+// compacted list, and the fillers a test per consecutive pair of final LCBs.
+// diag_diff <= 1 (a ratio): the test has two outcomes, a MUM joins the open chain or closes it, so the chain's last MUM is always
+// the list predecessor, a chain boundary is a flag per consecutive pair and the chains are the maximal runs between "close" verdicts.
+// diag_diff > 1 (bases, :2684-2692): a MUM whose gaps differ by diag_diff or more neither joins nor closes -- it is PASSED, and
+// the next MUM is judged against the chain's last joined MUM.  The verdicts against the list predecessor (v0) are still final
+// wherever no passed MUM lies just before: a WINDOW begins at every x with v0(x) = pass whose predecessor was not passed, its MUMs
+// x, x + 1, ... are judged against the fixed back x - 1 until the first that joins or closes (z), and from z + 1 on the
+// predecessor is the back again.  Every x with v0(x) = pass walks its window (ChainWindow: speculative, the walks do not depend
+// on one another); one lane keeps, in list order, the starts that no earlier kept window covers (ChainSelect: every position of
+// a kept window but its last IS passed, so a start inside it had a false premise); the kept windows write their verdicts and
+// backs (ChainWindowFill).  A passed MUM is in no LCB, adds to no length, is never dissolved, stays in the list of the second pass.
+// The host receives the sorted rows of the final MUM list, a byte per MUM (member, head, in no LCB) and seven counters; what is
+// not order-free (a tie), a window longer than the cap or more starts than kChainStarts is reported in the trouble word and the
+// caller runs its own list logic instead -- nothing on the device has changed by then.
+constexpr uint8_t kChJoin = 0, kChClose = 1, kChPass = 2;
+constexpr uint64_t kChainTie = 1, kChainOverrun = 2, kChainOrder = 4, kChainWindow = 8;      // (kChainOrder: the order check, ForeignBound and the kernels around it, queued ahead of the chain kernels)
+constexpr int64_t kChainStarts = 1 << 16;          // window starts of one pass that the engine lists
+constexpr int64_t kChainWindowMax = 1 << 16;       // the largest settable cap of a window (passed MUMs in a row); the default is 4 096
 // the header of a chain call (int64 words in device memory)
-enum { kChN1 = 0, kChLcb1, kChLcbDissolved, kChMumDissolved, kChN2, kChLcb2, kChFill, kChTrouble, kChWords };
+enum { kChN1 = 0, kChLcb1, kChLcbDissolved, kChMumDissolved, kChN2, kChLcb2, kChFill, kChTrouble, kChPass1, kChPass2, kChWords };
 // tid = store row (one past the end: 0): accepted?
 struct ChainFlag {
     Store S; int64_t rows; int64_t* flag;
@@ -1947,116 +1958,182 @@ struct ChainKeys {
         key[pos[c]] = (uint64_t)(uint32_t)(S.start[c * S.ngen] + S.shift[c]); val[pos[c]] = (uint64_t)c;
     }
 };
-// One wavefront per list position x: the test of setFinalClusters (:2596-2700) of MUM row[x] against row[x - 1], to the verdict.
-// All-forward pairs are a reduction over the genomes (JudgePairs) and the ratio test of :2693 in the reference's float / double
-// mix; a pair with a reverse member is left to ChainJudgeReverse (the strand rules of :2604-2625 and `max_gap = fgap` at :2608-2611
-// depend on the genome order: one lane walks the genomes).  *count: the list's length (the launch covers its capacity).
+// the test of :2684-2700 on the two gaps the loop over the genomes left, in the reference's float / double mix: a ratio (diag_diff <= 1)
+// joins or closes, a difference in bases (diag_diff > 1) joins or passes.  The 0 -> 1 substitution comes first in both
+PM_HD uint8_t chain_gap_test(float min_gap, float max_gap, float diag_diff) {
+    if (min_gap == 0) min_gap = 1;
+    if (max_gap == 0) max_gap = 1;
+    if (diag_diff > 1.0) return max_gap - min_gap < diag_diff ? kChJoin : kChPass;
+    return min_gap / max_gap >= 1.0 - diag_diff ? kChJoin : kChClose;
+}
+// the test of setFinalClusters (:2596-2700) of MUM row a against the chain's last MUM row b, neither with a reverse member: a
+// reduction over the genomes (JudgePairs), by all lanes of a wavefront; the verdict is wave-uniform
+PM_HD uint8_t chain_judge_forward(const Store& S, int64_t a, int64_t b, int32_t d, float diag_diff) {
+    const int n = S.ngen;
+    const int64_t sa = S.shift[a], sb = S.shift[b], lb = S.len[b];
+    int32_t mn = 0x7fffffff, mx = -0x7fffffff;
+    uint32_t bad = 0;
+    lanes_for(0, n, [&](int j) {
+        const int64_t g = ((int64_t)S.start[a * n + j] + sa) - ((int64_t)S.start[b * n + j] + sb + lb);
+        if (g < 0 || g > d) bad = 1;
+        const int32_t gi = g < -0x7fffffff ? -0x7fffffff : g > 0x7fffffff ? 0x7fffffff : (int32_t)g;
+        if (gi < mn) mn = gi;
+        if (gi > mx) mx = gi;
+    });
+    bad = wave_or_u32(bad); mn = wave_min_i32(mn); mx = wave_max_i32(mx);
+    if (bad) return kChClose;
+    // every gap in [0, d]: the loop leaves max_gap = the largest gap (from 0) and min_gap = the smallest (from d + 10)
+    float max_gap = 0, min_gap = (float)(d + 10);
+    if ((float)mx > max_gap) max_gap = (float)mx;
+    if ((float)mn < min_gap) min_gap = (float)mn;
+    return chain_gap_test(min_gap, max_gap, diag_diff);
+}
+// the same test for a pair with a reverse-strand member, genome by genome -- the strand rules of :2604-2625 and the `max_gap = fgap`
+// of :2608-2611 make the loop's outcome depend on the order of the genomes, so ONE lane walks them
+PM_HD uint8_t chain_judge_reverse(const Store& S, int64_t a, int64_t b, int32_t d, float diag_diff) {
+    const int n = S.ngen;
+    const int64_t sa = S.shift[a], la = S.len[a], sb = S.shift[b], lb = S.len[b];
+    float max_gap = 0, min_gap = (float)(d + 10);
+    for (int k = 0; k < n; k++) {
+        const int64_t ns = (int64_t)S.start[a * n + k] + sa, bs = (int64_t)S.start[b * n + k] + sb;
+        const int64_t fgap = ns - (bs + lb);        // forward: next start - chain end
+        const int64_t rgap = bs - (ns + la);        // reverse: previous MUM start - next end
+        const bool f = S.strand[a * n + k] != 0;
+        if (f && fgap > max_gap) max_gap = (float)fgap;
+        else if (!f && rgap > max_gap) max_gap = (float)fgap;       // sic (:2608-2611)
+        if (f && fgap < min_gap) min_gap = (float)fgap;
+        else if (!f && rgap < min_gap) min_gap = (float)rgap;
+        if (S.strand[a * n + k] != S.strand[b * n + k]) return kChClose;
+        if (f ? (fgap < 0 || fgap > d) : (fgap >= 0 || rgap > d)) return kChClose;
+    }
+    return chain_gap_test(min_gap, max_gap, diag_diff);
+}
+// One wavefront per list position x: the test of MUM row[x] against row[x - 1], to the verdict (v0 where diag_diff > 1).  All-forward
+// pairs here; a pair with a reverse member is left to ChainJudgeReverse.  *count: the list's length (the launch covers its capacity).
+// back (diag_diff > 1 only, else null): the position of the MUM that x is judged against, x - 1 until a window says otherwise.
 struct ChainJudge {
     Store S; const uint64_t* key; const uint64_t* row; const int64_t* count; int32_t d; float diag_diff; uint8_t* verdict; uint64_t* trouble;
     int force_tie;      // (tests) report a tie although there is none: the caller's own list logic takes over
+    int64_t* back;
     PM_HD void wave(int64_t x) const {
         if (x >= *count) return;
+        if (back && wave_leader()) back[x] = x > 0 ? x - 1 : 0;
         if (x == 0) { if (wave_leader()) { verdict[0] = kChClose; if (force_tie) atomic_or64(trouble, kChainTie); } return; }
         const int64_t a = (int64_t)row[x], b = (int64_t)row[x - 1];
-        const int n = S.ngen;
         if (key[x] == key[x - 1] && wave_leader()) atomic_or64(trouble, kChainTie);
-        const int64_t sa = S.shift[a], la = S.len[a], sb = S.shift[b], lb = S.len[b];
-        uint8_t out = kChClose;
-        if (!((S.flags[a] | S.flags[b]) & kRowReverse)) {
-            int32_t mn = 0x7fffffff, mx = -0x7fffffff;
-            uint32_t bad = 0;
-            lanes_for(0, n, [&](int j) {
-                const int64_t g = ((int64_t)S.start[a * n + j] + sa) - ((int64_t)S.start[b * n + j] + sb + lb);
-                if (g < 0 || g > d) bad = 1;
-                const int32_t gi = g < -0x7fffffff ? -0x7fffffff : g > 0x7fffffff ? 0x7fffffff : (int32_t)g;
-                if (gi < mn) mn = gi;
-                if (gi > mx) mx = gi;
-            });
-            bad = wave_or_u32(bad); mn = wave_min_i32(mn); mx = wave_max_i32(mx);
-            if (!bad) {
-                // every gap in [0, d]: the loop leaves max_gap = the largest gap (from 0) and min_gap = the smallest (from d + 10)
-                float max_gap = 0, min_gap = (float)(d + 10);
-                if ((float)mx > max_gap) max_gap = (float)mx;
-                if ((float)mn < min_gap) min_gap = (float)mn;
-                if (min_gap == 0) min_gap = 1;
-                if (max_gap == 0) max_gap = 1;
-                out = min_gap / max_gap >= 1.0 - diag_diff ? kChJoin : kChClose;
-            }
-        } else return;      // (a reverse member: ChainJudgeReverse)
+        if ((S.flags[a] | S.flags[b]) & kRowReverse) return;      // (a reverse member: ChainJudgeReverse)
+        const uint8_t out = chain_judge_forward(S, a, b, d, diag_diff);
         if (wave_leader()) verdict[x] = out;
     }
 };
-// tid = list position x: the same test for a pair with a reverse-strand member, genome by genome -- the strand rules of :2604-2625 and
-// the `max_gap = fgap` of :2608-2611 make the loop's outcome depend on the order of the genomes, so ONE lane walks them; but the pairs
-// do not depend on one another, so every lane of the launch has a pair of its own (a lane of a wavefront per pair until round 6: 7 ms for
-// the 60 000 pairs of 500 rearranged genomes, and 63 lanes idle).  A lane streams its two rows, 64-byte lines of 16 genomes each.
+// tid = list position x: the pairs with a reverse-strand member.  The pairs do not depend on one another, so every lane of the launch
+// has a pair of its own (a lane of a wavefront per pair until round 6: 7 ms for the 60 000 pairs of 500 rearranged genomes, and 63
+// lanes idle).  A lane streams its two rows, 64-byte lines of 16 genomes each.
 struct ChainJudgeReverse {
     Store S; const uint64_t* row; const int64_t* count; int32_t d; float diag_diff; uint8_t* verdict;
     PM_HD void operator()(int64_t x) const {
         if (x < 1 || x >= *count) return;
         const int64_t a = (int64_t)row[x], b = (int64_t)row[x - 1];
         if (!((S.flags[a] | S.flags[b]) & kRowReverse)) return;
-        const int n = S.ngen;
-        const int64_t sa = S.shift[a], la = S.len[a], sb = S.shift[b], lb = S.len[b];
-        uint8_t out = kChClose;
-        bool addmum = true;
-        float max_gap = 0, min_gap = (float)(d + 10);
-        for (int k = 0; k < n; k++) {
-            const int64_t ns = (int64_t)S.start[a * n + k] + sa, bs = (int64_t)S.start[b * n + k] + sb;
-            const int64_t fgap = ns - (bs + lb);        // forward: next start - chain end
-            const int64_t rgap = bs - (ns + la);        // reverse: previous MUM start - next end
-            const bool f = S.strand[a * n + k] != 0;
-            if (f && fgap > max_gap) max_gap = (float)fgap;
-            else if (!f && rgap > max_gap) max_gap = (float)fgap;       // sic (:2608-2611)
-            if (f && fgap < min_gap) min_gap = (float)fgap;
-            else if (!f && rgap < min_gap) min_gap = (float)rgap;
-            if (S.strand[a * n + k] != S.strand[b * n + k]) addmum = false;
-            else if (f && fgap < 0) addmum = false;
-            else if (!f && fgap >= 0) addmum = false;
-            else if (f && fgap > d) addmum = false;
-            else if (!f && rgap > d) addmum = false;
-            if (!addmum) break;
-        }
-        if (addmum) {
-            if (min_gap == 0) min_gap = 1;
-            if (max_gap == 0) max_gap = 1;
-            out = min_gap / max_gap >= 1.0 - diag_diff ? kChJoin : kChClose;
-        }
-        verdict[x] = out;
+        verdict[x] = chain_judge_reverse(S, a, b, d, diag_diff);
     }
 };
-// tid = list position (capacity + 1 of them: the scan's closing word): does a chain begin here?
-struct ChainHeads {
-    const uint8_t* verdict; const int64_t* count; int64_t* head;
-    PM_HD void operator()(int64_t x) const { head[x] = x < *count && verdict[x] == kChClose ? 1 : 0; }
+// One wavefront per list position x with v0(x) = pass (diag_diff > 1): the window that would begin at x if x - 1 was not passed.
+// Its MUMs are judged against the fixed back x - 1, one after the other (at most `window` of them: a uniform bound, capped by
+// kChainWindowMax), to the first that is not passed: wend[x] = its position (*count: the list ends first; -1: the cap came first)
+// and wverdict[x] = its verdict.  A pair with a reverse member is walked by every lane alike (uniform addresses).  The wavefront
+// also enters x in the list of starts (wpos: the exclusive scan of the v0 = pass flags), while that list has room.
+struct ChainWindow {
+    Store S; const uint64_t* row; const int64_t* count; int32_t d; float diag_diff; const uint8_t* verdict; int64_t window; const int64_t* wpos;
+    int64_t* wlist; int64_t* wend; uint8_t* wverdict;
+    PM_HD void wave(int64_t x) const {
+        const int64_t n = *count;
+        if (x < 1 || x >= n || verdict[x] != kChPass) return;
+        const int64_t b = (int64_t)row[x - 1];
+        const bool brev = (S.flags[b] & kRowReverse) != 0;
+        int64_t end = -1;
+        uint8_t v = kChPass;
+        for (int64_t k = 1; k <= window; k++) {
+            const int64_t z = x + k;
+            if (z >= n) { end = n; break; }
+            const int64_t a = (int64_t)row[z];
+            v = brev || (S.flags[a] & kRowReverse) ? chain_judge_reverse(S, a, b, d, diag_diff) : chain_judge_forward(S, a, b, d, diag_diff);
+            if (v != kChPass) { end = z; break; }
+        }
+        if (!wave_leader()) return;
+        wend[x] = end; wverdict[x] = v;
+        if (wpos[x] < kChainStarts) wlist[wpos[x]] = x;
+    }
 };
-// tid = list position: the MUM's length into its LCB's sum (lcb = number of heads up to and including x, less one)
+// ONE lane: the starts in list order; a start is kept when no earlier kept window covers it (covered: up to and including the
+// position that ended that window, whose verdict is the window's).  A kept window that met the cap, or more starts than the list
+// holds: kChainWindow, and the caller's own list logic takes over.
+struct ChainSelect {
+    const int64_t* count; const int64_t* wpos; const int64_t* wlist; const int64_t* wend; uint8_t* keep; uint64_t* trouble;
+    PM_HD void operator()(int64_t) const {
+        const int64_t ns = wpos[*count];
+        if (ns > kChainStarts) { atomic_or64(trouble, kChainWindow); return; }
+        int64_t covered = 0;
+        for (int64_t i = 0; i < ns; i++) {
+            const int64_t x = wlist[i];
+            keep[i] = x > covered ? 1 : 0;
+            if (x <= covered) continue;
+            if (wend[x] < 0) { atomic_or64(trouble, kChainWindow); return; }
+            covered = wend[x];
+        }
+    }
+};
+// One wavefront per entry of the list of starts: a kept window writes its verdicts -- passed from its start to the MUM before its
+// end, the end's own verdict -- and x - 1 as the back of them all
+struct ChainWindowFill {
+    const int64_t* count; const int64_t* wpos; const int64_t* wlist; const int64_t* wend; const uint8_t* wverdict; const uint8_t* keep;
+    const uint64_t* trouble; uint8_t* verdict; int64_t* back;
+    PM_HD void wave(int64_t i) const {
+        if (*trouble & kChainWindow) return;      // (keep[] is not complete then)
+        const int64_t n = *count;
+        if (i >= wpos[n] || !keep[i]) return;
+        const int64_t x = wlist[i], e = wend[x];
+        lanes_for(0, (int)(e - x), [&](int k) { verdict[x + k] = kChPass; back[x + k] = x - 1; });
+        if (e < n && wave_leader()) { verdict[e] = wverdict[x]; back[e] = x - 1; }
+    }
+};
+// tid = list position (capacity + 1 of them: the scan's closing word): is the verdict `what` -- does a chain begin here (kChClose),
+// would a window (kChPass)?
+struct ChainHeads {
+    const uint8_t* verdict; const int64_t* count; int64_t* head; uint8_t what;
+    PM_HD void operator()(int64_t x) const { head[x] = x < *count && verdict[x] == what ? 1 : 0; }
+};
+// tid = list position: the MUM's length into its LCB's sum (lcb = number of heads up to and including x, less one); a passed MUM is
+// counted instead
 struct ChainLcbSum {
-    Store S; const uint64_t* row; const int64_t* count; const int64_t* hpos; uint64_t* lcb_len;
+    Store S; const uint64_t* row; const int64_t* count; const int64_t* hpos; const uint8_t* verdict; uint64_t* lcb_len; int64_t* hdr;
     PM_HD void operator()(int64_t x) const {
         if (x >= *count) return;
+        if (verdict[x] == kChPass) { atomic_add64((uint64_t*)&hdr[kChPass1], 1); return; }
         atomic_add64(&lcb_len[hpos[x + 1] - 1], (uint64_t)(int64_t)S.len[(int64_t)row[x]]);
     }
 };
 // tid = list position (capacity + 1): filterRandomClustersSimple1 (:433-497) -- an LCB whose MUM lengths sum to <= c is dissolved,
-// the last one is never examined (:447); survive[x] for the compaction, the two counters of the log
+// the last one is never examined (:447), a passed MUM belongs to none; survive[x] for the compaction, the two counters of the log
 struct ChainDissolve {
-    const int64_t* count; const int64_t* hpos; const int64_t* head; const uint64_t* lcb_len; int64_t c; int64_t* survive; int64_t* hdr;
+    const int64_t* count; const int64_t* hpos; const int64_t* head; const uint8_t* verdict; const uint64_t* lcb_len; int64_t c; int64_t* survive; int64_t* hdr;
     PM_HD void operator()(int64_t x) const {
         const int64_t n = *count;
         if (x >= n) { survive[x] = 0; return; }
         const int64_t nl = hpos[n], id = hpos[x + 1] - 1;
         if (x == 0) { hdr[kChN1] = n; hdr[kChLcb1] = nl; }
-        const bool dis = hdr[kChTrouble] == 0 && id != nl - 1 && (int64_t)lcb_len[id] <= c;
+        const bool dis = hdr[kChTrouble] == 0 && id != nl - 1 && (int64_t)lcb_len[id] <= c && verdict[x] != kChPass;
         survive[x] = dis ? 0 : 1;
         if (dis) { atomic_add64((uint64_t*)&hdr[kChMumDissolved], 1); if (head[x]) atomic_add64((uint64_t*)&hdr[kChLcbDissolved], 1); }
     }
 };
-// one wavefront per list position: a dissolved MUM leaves the layout (:460-466)
+// one wavefront per list position: a dissolved MUM leaves the layout (:460-466).  trouble (diag_diff > 1 only, else null): the
+// launch comes after the windows of the second pass, and leaves the layout alone when one of them had to report
 struct ChainUnmark {
-    Store S; Layout L; const uint64_t* row; const int64_t* count; const int64_t* survive;
+    Store S; Layout L; const uint64_t* row; const int64_t* count; const int64_t* survive; const uint64_t* trouble;
     PM_HD void wave(int64_t x) const {
         if (x >= *count || survive[x]) return;
+        if (trouble && *trouble) return;
         const int64_t c = (int64_t)row[x];
         const int64_t sh = S.shift[c], len = S.len[c];
         lanes_for(0, S.ngen, [&](int j) { const int64_t a = (int64_t)S.start[c * S.ngen + j] + sh; img_clear_range(L, j, a, a + len); });
@@ -2073,14 +2150,15 @@ struct ChainCompact {
     }
 };
 // One wavefront per list position of the final list: where an LCB begins (x >= 1), setInterClusterRegions (:2389-2460) for the
-// LCB that ends at x - 1 and the one that begins at x -- FillBetween without the rows, which nothing downstream reads (a
-// filler is never printed; it shifts the numbers of the LCBs behind it, :2452-2457).
+// LCB that ends before x and the one that begins at x -- FillBetween without the rows, which nothing downstream reads (a
+// filler is never printed; it shifts the numbers of the LCBs behind it, :2452-2457).  The earlier LCB's last MEMBER is x - 1, or
+// back[x] where passed MUMs may lie in between (the MUM that x was judged against, and closed).
 struct ChainFill {
-    Store S; Layout L; Packed P; const uint64_t* row; const int64_t* count; const int64_t* head; int64_t* hdr;
+    Store S; Layout L; Packed P; const uint64_t* row; const int64_t* count; const int64_t* head; const int64_t* back; int64_t* hdr;
     PM_HD void wave(int64_t w) const {
         const int64_t x = w + 1;
         if (x >= *count || !head[x]) return;
-        const int64_t ct = (int64_t)row[x - 1], nx = (int64_t)row[x];
+        const int64_t ct = (int64_t)row[back ? back[x] : x - 1], nx = (int64_t)row[x];
         const int n = S.ngen;
         const int64_t ce = (int64_t)S.shift[ct] + S.len[ct], ns = S.shift[nx];
         uint32_t overlap = 0, small = 0;
@@ -2101,14 +2179,17 @@ struct ChainFill {
         else if (!small) atomic_add64((uint64_t*)&hdr[kChFill], 1);
     }
 };
-// tid = list position: what the host receives -- the store row and the head flag of every MUM of the final list
+// tid = list position: what the host receives -- the store row of every MUM of the final list and a byte: 0 a member of the LCB
+// open at it, 1 the head of an LCB, 2 in no LCB (passed)
 struct ChainOut {
-    const uint64_t* row; const int64_t* count; const int64_t* head; const int64_t* hpos; int32_t* out_row; uint8_t* out_head; int64_t* hdr;
+    const uint64_t* row; const int64_t* count; const int64_t* head; const int64_t* hpos; const uint8_t* verdict; int32_t* out_row; uint8_t* out_head; int64_t* hdr;
     PM_HD void operator()(int64_t x) const {
         const int64_t n = *count;
         if (x == 0) hdr[kChLcb2] = hpos[n];
         if (x >= n) return;
-        out_row[x] = (int32_t)row[x]; out_head[x] = (uint8_t)head[x];
+        const bool passed = verdict[x] == kChPass;
+        if (passed) atomic_add64((uint64_t*)&hdr[kChPass2], 1);
+        out_row[x] = (int32_t)row[x]; out_head[x] = passed ? (uint8_t)2 : (uint8_t)head[x];
     }
 };
 

@@ -1863,6 +1863,7 @@ void Aligner::chain() {
     };
     Lcb cluster = open_chain(mums[0]);
     bool addmum = true;
+    long passed = 0;
     for (long x = 1; x < m; x++) {
         const long nt_length = lens[(size_t)x];
         if (nt_length < random) { addmum = true; continue; }
@@ -1870,7 +1871,7 @@ void Aligner::chain() {
         addmum = true;
         const int back = cluster.mums.back();
         const uint8_t v = back == mums[(size_t)x - 1] ? ahead[(size_t)x] : judge(mums[(size_t)x], back);
-        if (v == PASS) continue;
+        if (v == PASS) { passed++; continue; }
         if (v == JOIN) {
             cluster.length += nt_length;
             cluster.mums.push_back(mums[(size_t)x]);
@@ -1881,6 +1882,7 @@ void Aligner::chain() {
     }
     if (!addmum) cluster = open_chain(mums.back());
     close_chain(cluster);
+    if (stats.chain_passed < 0) stats.chain_passed = passed;      // (of the first chaining pass)
     stats.lcb_s += now_s() - t0;
 }
 

@@ -275,6 +275,7 @@ struct Stats {   // wall-clock split reported next to the reference's own phase 
     long regions_deferred = 0;      // (resident route) regions a generation left on the work list: their cluster met an earlier one in some genome, or a child sorted first
     long tie_runs = 0, tie_runs_open = 0;   // (resident route) runs of different regions with one reference start; ... of which more than one region had candidates (the route is left)
     long resident = 0;              // 1: phases A-D ran on the resident route (resident.cpp: rows, layout and regions stayed on the device)
+    long chain_passed = -1;         // MUMs that neither joined nor closed a chain in the first chaining pass (diag_diff in bases); -1: no pass has run
     long device_chain = 0;          // 1: phases C-D (sort, chaining, LCB filter, fillers) came from the device in one call (pm_store_chain_*)
     long resident_retry = 0;        // 1: the resident route was left (the reference's processing order would have shown) and the step ran again on the host route
     long tie_fallbacks = 0, literal_iterations = 0, parallel_candidates = 0, parallel_dirty = 0, parallel_tangled = 0;   // work-list ties between different regions (extend_pass)

@@ -1,6 +1,7 @@
 // main.cpp -- parsnp_core: same command line, .ini surface, phase order, outputs and exit codes as the
 // reference's main() (src/parsnp.cpp:2792-3299), with the MUM search running on the MI355X through
 // include/parsnp_mum.h.  Extra, off by default: PARSNP_TIMING=<file> writes a JSON line with the wall-clock split.
+#include "hooks.h"
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -105,6 +106,8 @@ int main(int argc, char* argv[]) {
         exit(run.mumi());
     }
     std::ofstream mfile((writer ? run.prm.outdir + "/parsnpAligner.log" : std::string("/dev/null")).c_str());
+    if (const char* k = test_hook("PARSNP_STEPS"))      // test hook: that many steps in this process; the last one is written (later steps reuse what the session keeps)
+        for (long i = 1; i < atol(k); i++) (void)run.step();
     StepReport rep = run.step();
     if (!writer) exit(0);          // every rank computed the same alignment; rank 0 writes it
     if (!rep.mums_found) {
@@ -141,7 +144,7 @@ int main(int argc, char* argv[]) {
                     "\"anchor_s\": %.6f, \"extend_s\": %.6f, \"filter_s\": %.6f, \"lcb_s\": %.6f, \"output_s\": %.6f, \"total_s\": %.6f, "
                     "\"finder_s\": %.6f, \"finder_calls\": %ld, \"finder_regions\": %ld, \"regions_processed\": %ld, \"cache_hits\": %ld, "
                     "\"cache_misses\": %ld, \"spec_rounds\": %ld, \"anchors\": %ld, \"mums\": %ld, \"lcbs\": %ld, \"core_bp\": %ld, "
-                    "\"gap_note\": %s, \"tie_fallbacks\": %ld, \"literal_iterations\": %ld, \"parallel_candidates\": %ld, \"parallel_dirty\": %ld, \"t_validate\": %.6f, \"t_neighbour\": %.6f, \"t_sweep\": %.6f, \"t_replay\": %.6f, \"t_key\": %.6f, \"resident\": %ld, \"resident_retry\": %ld, \"device_chain\": %ld, \"h2d_bytes\": %.0f, \"d2h_bytes\": %.0f, \"outside_writes\": %.0f, \"dense_regions\": %.0f, \"resident_why\": \"%s\", "
+                    "\"gap_note\": %s, \"tie_fallbacks\": %ld, \"literal_iterations\": %ld, \"parallel_candidates\": %ld, \"parallel_dirty\": %ld, \"t_validate\": %.6f, \"t_neighbour\": %.6f, \"t_sweep\": %.6f, \"t_replay\": %.6f, \"t_key\": %.6f, \"resident\": %ld, \"resident_retry\": %ld, \"device_chain\": %ld, \"chain_passed\": %ld, \"h2d_bytes\": %.0f, \"d2h_bytes\": %.0f, \"outside_writes\": %.0f, \"dense_regions\": %.0f, \"resident_why\": \"%s\", "
                     "\"gap_jobs\": %ld, \"gap_jobs_wide\": %ld, \"gap_longest\": %ld, \"gap_device_narrow\": %ld, \"gap_device_wide\": %ld, \"gap_host\": %ld, \"gap_host_s\": %.6f, "
                     "\"gap_device_narrow_ms\": %.3f, \"gap_device_wide_ms\": %.3f, \"gap_device_tall\": %ld, \"gap_device_tall_ms\": %.3f, "
                     "\"gap_jobs_long\": %ld, \"gap_device_long\": %ld, \"gap_device_long_ms\": %.3f, \"gap_device_long_tall\": %ld, \"gap_device_long_tall_ms\": %.3f}\n",
@@ -149,7 +152,7 @@ int main(int argc, char* argv[]) {
                     rep.lcb_s, output_s, now_s() - t_begin, rep.finder_s, rep.finder_calls, rep.finder_regions, rep.regions_processed,
                     rep.cache_hits, rep.cache_misses, rep.spec_rounds, rep.anchors, rep.mums, rep.lcbs, rep.core_bp, gap_note ? "true" : "false",
                     rep.host.tie_fallbacks, rep.host.literal_iterations, rep.host.parallel_candidates, rep.host.parallel_dirty, rep.host.t_validate, rep.host.t_neighbour, rep.host.t_sweep, rep.host.t_replay, rep.host.t_key,
-                    rep.host.resident, rep.host.resident_retry, rep.host.device_chain, rep.h2d_bytes, rep.d2h_bytes, outside_writes, dense_regions, why.c_str(),
+                    rep.host.resident, rep.host.resident_retry, rep.host.device_chain, rep.host.chain_passed, rep.h2d_bytes, rep.d2h_bytes, outside_writes, dense_regions, why.c_str(),
                     gap_counts.jobs, gap_counts.jobs_wide, gap_counts.longest, gap_counts.device_narrow, gap_counts.device_wide, gap_counts.host, gap_counts.host_s,
                     gap_counts.device_narrow_ms, gap_counts.device_wide_ms, gap_counts.device_tall, gap_counts.device_tall_ms,
                     gap_counts.jobs_long, gap_counts.device_long, gap_counts.device_long_ms, gap_counts.device_long_tall, gap_counts.device_long_tall_ms);

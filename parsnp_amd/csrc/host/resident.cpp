@@ -450,12 +450,15 @@ bool Aligner::resident_extend() {
 
 // Phases C-D on the device (pm_store_chain_begin / _end: the sort of filterRandom1 :338, setFinalClusters :2563-2719,
 // filterRandomClustersSimple1 :433-497, the second chaining pass :3261-3268, setInterClusterRegions :2389-2460) where their list
-// logic is order-free: diag_diff <= 1 (the ratio test joins or closes: the chain's last MUM is the list predecessor), a filter
-// length below every MUM's (accepted MUMs have >= 2 bases), and -- the device's own finding -- no two MUMs with one reference start.
+// logic is order-free: a filter length below every MUM's (accepted MUMs have >= 2 bases), and -- the device's own finding -- no
+// two MUMs with one reference start.  diag_diff in bases (> 1) included: the MUMs that neither join nor close a chain come back
+// as such (head byte 2), unless more of them follow one another than the engine walks (its "chain_window").
+// (the engine's count of them is reported where the provider of the ABI has the call: the CPU provider of the tests has no store)
+extern "C" int pm_store_chain_passed(const pm_session* s, int64_t* first_pass, int64_t* second_pass) __attribute__((weak));
 void Aligner::resident_chain_begin(size_t expect) {
     static const bool off = test_hook("PARSNP_NO_DEVICE_CHAIN") != nullptr;      // test hook: the host's list logic over pm_store_judge / _unmark / _fill
     res_.chain_queued = false;
-    if (off || expect == 0 || prm.random > 1 || !(prm.diag_diff <= 1.0f)) return;
+    if (off || expect == 0 || prm.random > 1 || prm.diag_diff != prm.diag_diff) return;
     const int rc = pm_store_chain_begin(session_, (int64_t)expect, (int32_t)prm.d, prm.diag_diff, (int64_t)prm.c);
     if (rc != PM_OK) engine_error("phases C-D on the device failed", rc);
     collect_engine_timing();
@@ -490,11 +493,16 @@ bool Aligner::resident_chain() {
         if (getenv("PARSNP_DEBUG_TIMERS")) fprintf(stderr, "[resident] phases C-D by the host's list logic: %s\n", res_.chain_why.c_str());
         return false;
     }
+    if (ci.trouble & 8) {      // (nothing on the device has changed, and the list is in order as it stands)
+        res_.chain_why = "more MUMs in a row that neither join nor close a chain than the engine follows";
+        if (getenv("PARSNP_DEBUG_TIMERS")) fprintf(stderr, "[resident] phases C-D by the host's list logic: %s\n", res_.chain_why.c_str());
+        return false;
+    }
     if (ci.trouble & 2) fatal("inter-cluster region bookkeeping would overrun in the reference");
     // The answer stays where the engine put it; what the step report needs -- the counts and the reference span of every LCB --
     // takes one pass over the head flags and two rows per LCB.  The lists themselves (mums, lcbs: an index per MUM, three vectors
     // per LCB) are written by build_lists() when someone reads them: the writer, beside its download of the rows.
-    if (ci.n_mums > ci.n_in || (ci.n_mums > 0 && !heads[0])) fatal("the device's MUM list does not begin with an LCB head, or is longer than the list it came from");
+    if (ci.n_mums > ci.n_in || (ci.n_mums > 0 && heads[0] != 1)) fatal("the device's MUM list does not begin with an LCB head, or is longer than the list it came from");
     const std::vector<int32_t>& of = res_.of_row;
     const int64_t top = (int64_t)of.size() - 1;
     auto record = [&](int64_t z) {
@@ -506,9 +514,11 @@ bool Aligner::resident_chain() {
     int64_t nheads = 0;
     for (int64_t x = 0; x < ci.n_mums;) {      // LCB by LCB: from a head to the MUM before the next one
         int64_t y = x + 1;
-        for (uint64_t w; y + 8 <= ci.n_mums && (memcpy(&w, heads + y, 8), w == 0);) y += 8;      // (eight flags at a time)
-        while (y < ci.n_mums && !heads[y]) y++;
-        const int first = record(x), last = record(y - 1);
+        for (uint64_t w; y + 8 <= ci.n_mums && (memcpy(&w, heads + y, 8), (w & 0x0101010101010101ull) == 0);) y += 8;      // (eight bytes at a time: none of them a head)
+        while (y < ci.n_mums && heads[y] != 1) y++;
+        int64_t z = y - 1;
+        while (heads[z] == 2) z--;      // (the LCB's last member: a MUM in no LCB may lie behind it; the head at x is one)
+        const int first = record(x), last = record(z);
         sm.core_bp += key0(last) + pool[(size_t)last].length - key0(first);
         nheads++;
         x = y;
@@ -523,6 +533,8 @@ bool Aligner::resident_chain() {
     stats.lcb_s += now_s() - t0;
     if (dbg) fprintf(stderr, "[resident chain] with summary %.6f s\n", now_s() - t0);
     stats.device_chain = 1;
+    int64_t p1 = 0, p2 = 0;
+    if (pm_store_chain_passed && pm_store_chain_passed(session_, &p1, &p2) == PM_OK) stats.chain_passed = (long)p1;
     return true;
 }
 
@@ -555,19 +567,23 @@ void Aligner::build_lists() {
     for (int64_t f = 0; f < ci.n_fillers; f++) { Lcb c; c.type = 0; c.length = 2; lcbs.push_back(std::move(c)); }      // (their rows: nothing reads them)
     for (int64_t x = 0; x < ci.n_mums;) {      // LCB by LCB: from a head to the MUM before the next one
         int64_t y = x + 1;
-        while (y < ci.n_mums && !heads[y]) y++;
+        while (y < ci.n_mums && heads[y] != 1) y++;
         lcbs.emplace_back();
         Lcb& c = lcbs.back(); c.type = 1;
         c.mums.resize((size_t)(y - x));
         int* out = c.mums.data(); int* all = mums.data() + x;
         long total = 0;
+        size_t members = 0;
         for (int64_t z = x; z < y; z++) {
             const int32_t row = rows[z];
             if (row < 0 || row > top || of[(size_t)row] < 0) fatal("the device's MUM list names a row the host does not hold");
             const int idx = of[(size_t)row];
-            out[z - x] = idx; all[z - x] = idx;
+            all[z - x] = idx;
+            if (heads[z] == 2) continue;      // (in the MUM list, in no LCB)
+            out[members++] = idx;
             total += len_of[(size_t)row];
         }
+        c.mums.resize(members);
         c.length = total;
         c.start.assign(1, key0(c.mums.front()));
         c.end.assign(1, key0(c.mums.back()) + pool[(size_t)c.mums.back()].length);
@@ -663,17 +679,23 @@ void Aligner::materialize() {
     const double t0 = now_s();
     std::vector<int32_t> rows; std::vector<int> who;
     if (res_.lists_pending) {
-        // a chain on the device: the rows to fetch are its answer as it stands (every MUM of the list is in exactly one LCB), so the
-        // lists are written by a helper thread while this one waits for the download (the thread makes no engine call)
-        rows.assign(res_.chain_rows, res_.chain_rows + res_.chain_info.n_mums);
+        // a chain on the device: the rows to fetch are its answer less the MUMs in no LCB (none unless diag_diff is in bases), so
+        // the lists are written by a helper thread while this one waits for the download (the thread makes no engine call)
+        std::vector<int64_t> at;      // (list position of every fetched row; left empty while every MUM is a member)
+        {
+            const int64_t nm = res_.chain_info.n_mums;
+            const uint8_t* heads = res_.chain_heads;
+            if (!memchr(heads, 2, (size_t)nm)) rows.assign(res_.chain_rows, res_.chain_rows + nm);
+            else for (int64_t z = 0; z < nm; z++) if (heads[z] != 2) { rows.push_back(res_.chain_rows[z]); at.push_back(z); }
+        }
         std::future<void> lists = std::async(std::launch::async, [this] { build_lists(); });
         int32_t* st = irows_.alloc(rows.size() * n + 1); uint8_t* fw = brows_.alloc(rows.size() * n + 1);
         const int rc = rows.empty() ? PM_OK : pm_store_rows(session_, rows.data(), 0, (int64_t)rows.size(), 0, st, fw);
         lists.get();
         if (rc != PM_OK) engine_error("cannot fetch the MUM rows", PM_EHIP);
-        if (mums.size() != rows.size()) fatal("the MUM list and the rows fetched for it differ");
+        if (at.empty() ? mums.size() != rows.size() : mums.size() < rows.size()) fatal("the MUM list and the rows fetched for it differ");
         for (size_t i = 0; i < rows.size(); i++) {
-            Mum& m = pool[(size_t)mums[i]];
+            Mum& m = pool[(size_t)mums[at.empty() ? i : (size_t)at[i]]];
             if (m.row != rows[i]) fatal("the MUM list and the rows fetched for it differ");
             m.start = st + i * n; m.fwd = fw + i * n;
         }

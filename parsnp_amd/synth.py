@@ -48,7 +48,7 @@ def _diverged_copy(rng, w, rate):
             return out
 
 
-def population(seed, n, n_genomes, div, indel_frac=0.0, sites=None, carry_seed=None, select=None, windows=None):
+def population(seed, n, n_genomes, div, indel_frac=0.0, sites=None, carry_seed=None, select=None, windows=None, indel_len=1):
     """-> (ref bytes, [genome bytes]) under the population model.  carry_seed: draw the genomes from a separate
     stream (same reference and site pool, different genomes -- one partition per rank in bench.py).  select: indices
     of the genomes to materialise (the random stream still advances over all of them, so genome i is the same bytes
@@ -58,7 +58,10 @@ def population(seed, n, n_genomes, div, indel_frac=0.0, sites=None, carry_seed=N
     every genome -- or each of `haplotypes` haplotypes, dealt to the genomes at random -- carries an independently diverged copy
     (_diverged_copy) at a rate drawn from `div`; `flank` bases on either side carry no segregating site, so that the flanks are
     MUMs of one cluster and the window is a gap of 97 to about 290 bases between them (the gaps a default run, d = 300, hands
-    to the gap aligner on real genomes).  The windows draw from a stream of their own."""
+    to the gap aligner on real genomes).  The windows draw from a stream of their own.
+    indel_len (default 1: the sets are what they have always been): a deletion takes 1 to indel_len bases from its site on, the
+    length drawn per site from a stream of its own -- the MUMs on its two sides lie that many bases off one diagonal in the
+    genomes that carry it (what a diagonal difference given in bases, diagdiff > 1, is about)."""
     rng = np.random.default_rng(seed)
     ref = random_genome(rng, n)
     if sites is None:
@@ -82,6 +85,7 @@ def population(seed, n, n_genomes, div, indel_frac=0.0, sites=None, carry_seed=N
         sites = sites[~clear[sites]]
     alt = _alt(rng, ref[sites])
     is_del = rng.random(len(sites)) < indel_frac
+    del_len = np.ones(len(sites), dtype=np.int64) if indel_len <= 1 else np.random.default_rng([seed, 0x64656c]).integers(1, indel_len + 1, len(sites))
     if carry_seed is not None:
         rng = np.random.default_rng(carry_seed)
     out = []
@@ -94,6 +98,9 @@ def population(seed, n, n_genomes, div, indel_frac=0.0, sites=None, carry_seed=N
         g[sub] = alt[carry & ~is_del]
         keep = np.ones(n, dtype=bool)
         keep[sites[carry & is_del]] = False
+        if indel_len > 1:
+            for at, ln in zip(sites[carry & is_del], del_len[carry & is_del]):
+                keep[at:at + ln] = False
         if win:
             parts, prev = [], 0
             for a, length, copies, deal in win:
