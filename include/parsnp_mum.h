@@ -178,7 +178,20 @@ int64_t pm_result_table_id(const pm_result* r);
  *   "chain_tie"    != 0: pm_store_chain_begin reports two MUMs with one reference start although there is none (tests: the
  *                  caller's own list logic must give the same bytes)
  *   "timing"       0: no HIP events around the phases of a call (pm_last_timing then reports counts only)
- * PM_EINVAL for an unknown key or a value out of range. */
+ *   "index_build"  0: the reference index of every region is built by IndexInsert (compare-and-swap in global memory) as before; default 1: a
+ *                  region with "index_bucket_min" slots or more is built by buckets in LDS (index_kernels.h: keys sorted by bucket, a
+ *                  wavefront per bucket, the table and the filter written once); the same multi-MUMs either way, tests compare the two
+ *   "index_bucket_min" slots of the smallest table that "index_build" = 1 builds by buckets (default 2^24: a region of more than 4 194 304
+ *                  bases at the default "slot_factor", the shape the build was measured at; tests and measurements lower it); a smaller region, or one whose filter piece per bucket would be under 32 bits
+ *                  or over 16 384, is built by IndexInsert in the same launch as before
+ *   "index_verify" != 0: after the index build a kernel looks every reference position up again (its K-mer's slot found, the
+ *                  position on that slot's chain, the filter word passing, next = -1 outside chains) and pm_last_timing reports the
+ *                  violations as "index_lost" (tests; default 0)
+ *   "index_overflow_cap" capacity of the bucket build's overflow list in records (0, the default: a 32nd of the bucketed
+ *                  positions + 1 024); a list that is full makes the call build every region with IndexInsert (tests set it to 1)
+ * PM_EINVAL for an unknown key or a value out of range.
+ * PARSNP_TUNE="key=value,key=value" in the environment applies these to every session from its start, the sessions that
+ * pm_find_events opens for itself included; an unknown key or a refused value fails the session's creation with PM_EINVAL. */
 int pm_session_tune(pm_session* s, const char* key, int64_t value);
 
 /* ---------------------------------------------------------------------------------------------------------------------------
@@ -459,7 +472,10 @@ int pm_gap_limits_long_tall(int* max_seqs, int* max_seq_len, int* max_cols);
  * A call that took the suffix-array path (see "work_budget") also reports the counts "dense_regions" (regions on the path) and
  * "dense_rounds" (prefix-doubling rounds of its sort), the phases "dense_sa" (suffix array + rep') and "dense_search" (its
  * events), and "dense_overrun" (wall ms of the pass that ran out of budget before it; not with "dense_all").  Other calls
- * report none of these keys. */
+ * report none of these keys.
+ * Counts of the index build (see "index_build"): "index_bucketed" -- reference positions of the regions whose index was built by
+ * buckets in LDS (0 after a full overflow list sent the call back to IndexInsert); "index_overflow" -- records of them whose probe
+ * run reached their bucket's end and went through the overflow list; "index_lost" -- only with "index_verify": its violations. */
 int pm_last_timing(const pm_session* s, int* count, const char** names, float* ms);
 
 /* The limits of the kernels that find the events of a recursion batch's small regions (every side at most 128 bases) once per

@@ -40,6 +40,18 @@ static int session_create(pm_session** out, int device, int n_genomes, const uin
         if (getenv("PARSNP_DEBUG_TIMERS")) fprintf(stderr, "[upload] %-14s %.4f s\n", "runtime start", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
         s->engine.reset(new pm::Engine<PmBackend>(*s->backend));
         if (coll) s->engine->set_shard(*coll);
+        // PARSNP_TUNE="key=value,key=value": pm_session_tune for every session from its start, the ones that entry points open for
+        // themselves (pm_find_events) included; an unknown key or a refused value is an error
+        if (const char* tn = getenv("PARSNP_TUNE")) {
+            std::string all(tn);
+            for (size_t at = 0; at < all.size();) {
+                size_t end = all.find(',', at); if (end == std::string::npos) end = all.size();
+                const std::string kv = all.substr(at, end - at); const size_t eq = kv.find('=');
+                at = end + 1;
+                if (kv.empty()) continue;
+                if (eq == std::string::npos || !s->engine->tune(kv.substr(0, eq), atoll(kv.c_str() + eq + 1))) return fail(PM_EINVAL, "PARSNP_TUNE: unknown tunable or bad value: " + kv);
+            }
+        }
         int rc = s->engine->load_genomes(n_genomes, seqs, lens);
         if (rc) return fail(rc, s->engine->error);
         if (!s->backend->ok()) return fail(PM_EHIP, s->backend->error());
@@ -346,6 +358,9 @@ int pm_last_timing(const pm_session* cs, int* count, const char** names, float* 
     s->timing.push_back(pm::PhaseTime{"n_grouped_wide", (float)s->engine->last_grouped_wide});      // of n_grouped, the events the wide form wrote
     s->timing.push_back(pm::PhaseTime{"n_wide_regions", (float)s->engine->last_wide_regions});      // regions the wide form took
     s->timing.push_back(pm::PhaseTime{"n_handed_back", (float)s->engine->last_handed_back});        // small regions neither form took (-1: the wide form, which counts them, did not run)
+    s->timing.push_back(pm::PhaseTime{"index_bucketed", (float)s->engine->last_index_bucketed});    // reference positions whose index was built by buckets in LDS
+    s->timing.push_back(pm::PhaseTime{"index_overflow", (float)s->engine->last_index_overflow});    // ... records of them that went through the overflow list
+    if (s->engine->last_index_lost >= 0) s->timing.push_back(pm::PhaseTime{"index_lost", (float)s->engine->last_index_lost});      // tune index_verify: violations IndexVerify counted
     if (s->engine->outside_writes) { s->timing.push_back(pm::PhaseTime{"outside_writes", (float)s->engine->outside_writes}); s->engine->outside_writes = 0; }      // accepted members outside their region, checked against the order (OutsideWriteCheck)
     if (s->engine->exact_cluster_tests) { s->timing.push_back(pm::PhaseTime{"exact_cluster_tests", (float)s->engine->exact_cluster_tests}); s->engine->exact_cluster_tests = 0; }      // generations validated with the exact test of their clusters (inversions)
     if (s->engine->tail_repeats) { s->timing.push_back(pm::PhaseTime{"tail_repeats", (float)s->engine->tail_repeats}); s->engine->tail_repeats = 0; }      // searches that repeated a part because a capacity from the last step was too small

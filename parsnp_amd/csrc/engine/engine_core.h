@@ -19,6 +19,7 @@
 #include "kernels.h"
 #include "store_kernels.h"
 #include "dense_kernels.h"
+#include "index_kernels.h"
 
 namespace pm {
 
@@ -188,7 +189,14 @@ public:
         const int64_t ordinal = call_ordinal;
         if (dense_all && nreg > 0) { dense_h.assign((size_t)nreg, 1); dense_mode = true; }
         const auto t0 = std::chrono::steady_clock::now();
+        index_rebuild = false;
         int rc = run_once(nreg, starts, lens, minsize, out, want_events, mumi, gb);
+        if (rc == kIndexRebuild) {      // the overflow list of the bucket build was full: the same call, every region built by IndexInsert
+            (void)be.collect();
+            call_ordinal = ordinal;
+            index_rebuild = true;
+            rc = run_once(nreg, starts, lens, minsize, out, want_events, mumi, gb);
+        }
         if (rc == -5 && budget_exceeded && !dense_mode) {
             budget_retries++;
             last_dense_overrun_ms = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -199,8 +207,14 @@ public:
             call_ordinal = ordinal;      // (the same call of the step: the same capacities)
             dense_mode = true; budget_exceeded = false;
             rc = run_once(nreg, starts, lens, minsize, out, want_events, mumi, gb);
+            if (rc == kIndexRebuild) {
+                (void)be.collect();
+                call_ordinal = ordinal;
+                index_rebuild = true;
+                rc = run_once(nreg, starts, lens, minsize, out, want_events, mumi, gb);
+            }
         }
-        dense_mode = false;
+        dense_mode = false; index_rebuild = false;
         return rc;
     }
     bool dense_all = false;             // pm_session_tune "dense_all": every region of every batch takes the suffix-array path (tests)
@@ -210,6 +224,9 @@ public:
     int64_t anchor_table_id = 0, anchor_table_rows = 0;      // the anchor table: rows of the last long one-region call in row mode = rows [0, A) of the MUM store
     bool budget_exceeded = false;
     long budget_retries = 0;
+    static constexpr int kIndexRebuild = -99;      // run_once: the bucket build's overflow list was full (never leaves run())
+    bool index_rebuild = false;                    // this run of the batch builds every region with IndexInsert
+    int64_t index_overflow_seen = 0;               // ... after a bucket build that left this many overflow records
     int run_once(int64_t nreg, const int64_t* starts, const int64_t* lens, const int32_t* minsize, BatchResult* out, bool want_events,
                  bool mumi, const GapBatch* gb = nullptr) {
         timing.clear();
@@ -290,6 +307,9 @@ public:
             if (b & 2) { error = "region longer than 2^31"; return -5; }
         }
         int64_t npos = 0, tsize = 0, fwords = 0, nunits = 0;
+        int64_t tsize_b = 0, fwords_b = 0, nbk = 0, npos_bucketed = 0;      // of the regions built by buckets: slots, filter words, buckets, positions
+        std::vector<int64_t> bbase(regz + 1, 0);                            // first bucket of every region
+        const bool by_index_buckets = index_build && !index_rebuild;
         int32_t max_nr = 1;
         size_t ev_guess = 1 << 16;     // first-call event buffer: a match of length >= minsize every max(8,minsize) bases is generous
         cbase[0] = 0;
@@ -304,10 +324,20 @@ public:
             int64_t slots = 16;
             while (slots < slot_factor * (int64_t)ri.nR) slots <<= 1;   // load factor <= 1 / slot_factor (x2: the next power of two)
             ri.tmask = (uint32_t)(slots - 1);
-            ri.tbase = tsize; tsize += slots;
             int64_t fbits = 64;
             while (fbits < filter_factor * (int64_t)ri.nR) fbits <<= 1;
-            ri.fmask = (uint32_t)(fbits - 1); ri.fbase = fwords; fwords += fbits / 32; ri.pad_ = 0;
+            ri.fmask = (uint32_t)(fbits - 1);
+            // built by buckets (index_kernels.h): a table of index_bucket_min slots or more, in buckets of at most kBucketSlots slots
+            // (two buckets at least), if a bucket's piece of the filter is a 32-bit word or more and fits the wavefront's LDS
+            const int ls = bits_for((uint64_t)slots) - 1, lf = bits_for((uint64_t)fbits) - 1;
+            const int sb = std::min(kBucketBits, ls - 1), fb = lf - (ls - sb);
+            const bool bucketed = by_index_buckets && slots >= index_bucket_min && fb >= 5 && fb <= kBucketFilterBits;
+            ri.pad_ = bucketed ? (uint32_t)sb | ((uint32_t)fb << 8) | kBucketed : (uint32_t)ls | ((uint32_t)std::min(lf, 29) << 8);
+            bbase[(size_t)r] = nbk;
+            if (bucketed) { nbk += slots >> sb; npos_bucketed += ri.nR; }
+            // the slices of the bucketed regions lie behind the others': the build writes them whole, only the others are cleared
+            ri.tbase = bucketed ? -1 - tsize_b : tsize; (bucketed ? tsize_b : tsize) += slots;
+            ri.fbase = bucketed ? -1 - fwords_b : fwords; (bucketed ? fwords_b : fwords) += fbits / 32;
             ri.posbase = npos; posbase[(size_t)r] = npos; npos += ri.nR;
             cbase[(size_t)r + 1] = cbase[(size_t)r] + (((int64_t)ri.nR + kChunkPos - 1) >> kCoarseShift) + 1;
             max_nr = std::max(max_nr, ri.nR);
@@ -315,6 +345,14 @@ public:
             nunits += units_r[(size_t)r];
         }
         posbase[regz] = npos;
+        bbase[regz] = nbk;
+        const int64_t tsize_clear = tsize, fwords_clear = fwords;
+        for (int64_t r = 0; r < nreg; r++) {
+            RegionInfo& ri = R[(size_t)r];
+            if (ri.tbase < 0) { ri.tbase = tsize_clear + (-1 - ri.tbase); ri.fbase = fwords_clear + (-1 - ri.fbase); }
+        }
+        tsize += tsize_b; fwords += fwords_b;
+        last_index_bucketed = npos_bucketed; last_index_overflow = index_rebuild ? index_overflow_seen : 0; last_index_lost = -1;
         last_positions = npos; last_candidates = 0; last_accepted = 0; last_grouped = 0; last_grouped_wide = 0; last_handed_back = -1; last_wide_regions = 0;
         const int64_t npairs = nreg * nq;
         const int64_t nchunks = cbase[regz] - nreg;                  // 256-position chunks of the batch
@@ -362,7 +400,7 @@ public:
         {
             // (the regions' dense flags as well -- but in the suffix-array run, which sets them from the host below)
             const ClearJob jobs[] = {
-                {d_filter.p, sizeof(uint32_t) * (size_t)fwords, 0}, {d_slots.p, sizeof(uint64_t) * (size_t)tsize, 0xff}, {d_counter.p, 8 * ncounter, 0},
+                {d_filter.p, sizeof(uint32_t) * (size_t)fwords_clear, 0}, {d_slots.p, sizeof(uint64_t) * (size_t)tsize_clear, 0xff}, {d_counter.p, 8 * ncounter, 0},
                 {d_repeated.p, 4 * (size_t)(npos / 32 + 2), 0}, {d_coarse.p, 4 * (size_t)std::max<int64_t>(centries, 1), 0},
                 {d_ucount.p + npairs, 8, 0}, {d_wcount.p + nwv, 8, 0}, {from_store_ ? d_alg.p : nullptr, from_store_ ? (size_t)64 * kAlgSets : 0, 0},
                 {dense_mode ? nullptr : d_dense.p, dense_mode ? 0 : regz, 0}};
@@ -382,7 +420,29 @@ public:
             be.launch_wave("alg_bytes", (nreg * nq + kAlgPairs - 1) / kAlgPairs, AlgBytes{d_R.p, d_lens.p, ngen, nreg * nq, d_alg.p});
         }
         be.mark("index");
-        be.launch("index_insert", npos, IndexInsert{P, d_R.p, nreg, d_posbase.p, d_slots.p, d_next.p, d_filter.p, d_rep.p});
+        const size_t kOvfSlot = (size_t)kSlices * kSliceStride + 6, kLostSlot = kOvfSlot + 1;      // (d_counter: overflow records of the bucket build, IndexVerify's count)
+        const uint64_t ovf_cap = nbk > 0 ? (uint64_t)(index_overflow_cap > 0 ? index_overflow_cap : npos_bucketed / 32 + 1024) : 0;
+        if (nbk > 0) {
+            // the bucketed regions (index_kernels.h): keys, sorted by bucket, a wavefront per bucket, then the overflow records
+            const int pbits = bits_for((uint64_t)npos), bbits = bits_for((uint64_t)nbk);
+            if (pbits + bbits > 64) { error = "batch too large for 64-bit index keys"; return -5; }
+            ensure(d_bkbase, regz + 1); ensure(d_ikey, (size_t)npos); ensure(d_ikey2, (size_t)npos); ensure(d_bkbegin, (size_t)nbk + 1); ensure(d_ovf, (size_t)ovf_cap);
+            be.h2d(d_bkbase.p, bbase.data(), 8 * (regz + 1));
+            be.launch("index_keys", npos, IndexKeys{P, d_R.p, nreg, d_posbase.p, d_bkbase.p, pbits, d_ikey.p, d_next.p, d_rep.p});
+            if (!sort_keys_on(be, d_ikey.p, d_ikey2.p, (size_t)npos, pbits, pbits + bbits, 0)) {
+                // a backend without sort_keys (the emulation): the keys as the values of a pair sort by their bucket number
+                ensure(d_ikey3, (size_t)npos); ensure(d_ikey4, (size_t)npos);
+                be.launch("index_key_buckets", npos, IndexKeyBuckets{d_ikey.p, pbits, d_ikey3.p});
+                be.sort_pairs(d_ikey3.p, d_ikey4.p, d_ikey.p, d_ikey2.p, (size_t)npos, bbits);
+            }
+            be.launch("index_bucket_bounds", nbk + 1, IndexBucketBounds{d_ikey2.p, npos, pbits, d_bkbegin.p});
+            be.launch_wave("index_bucket_fill", nbk, IndexBucketFill{P, d_R.p, nreg, d_bkbase.p, d_ikey2.p, d_bkbegin.p, pbits, d_slots.p, d_filter.p, d_next.p, d_rep.p,
+                                                                     d_counter.p + kOvfSlot, d_ovf.p, ovf_cap});
+            be.launch("index_overflow", (int64_t)ovf_cap, IndexOverflow{P, d_R.p, nreg, d_posbase.p, d_counter.p + kOvfSlot, d_ovf.p, ovf_cap, d_slots.p, d_next.p, d_rep.p});
+        }
+        if (npos_bucketed < npos) be.launch("index_insert", npos, IndexInsert{P, d_R.p, nreg, d_posbase.p, d_slots.p, d_next.p, d_filter.p, d_rep.p});
+        if (index_verify) be.launch("index_verify", npos, IndexVerify{P, d_R.p, nreg, d_posbase.p, d_slots.p, d_filter.p, d_next.p, d_counter.p + kLostSlot});
+        bool index_counts_read = false;
         be.mark("repeat");
         ensure(d_run, (size_t)std::max<int64_t>(npos, 1));
         be.launch("run_length", npos, RunLength{P, d_R.p, nreg, d_posbase.p, d_run.p});
@@ -489,6 +549,12 @@ public:
             if (!units_known) be.d2h_async(&nunits_live, d_uoff.p + npairs, 8);
             run_beside();      // (the caller's host work that needs nothing of this call: the device is busy with the event search)
             be.d2h(counts.data(), d_counter.p, 8 * counts.size());            // round trip 1: event counts + error word (+ the queues' lengths, + the unit count)
+            if (!index_counts_read) {      // (the first pass of this loop: a repeat clears the counters)
+                index_counts_read = true;
+                if (nbk > 0) last_index_overflow = (int64_t)counts[kOvfSlot];
+                if (index_verify) last_index_lost = (int64_t)counts[kLostSlot];
+                if (nbk > 0 && counts[kOvfSlot] > ovf_cap) { index_overflow_seen = (int64_t)counts[kOvfSlot]; return kIndexRebuild; }
+            }
             if (!units_known) {
                 units_known = true;
                 if (nunits_live >= (1ll << 31)) { error = "too many work units in one batch"; return -5; }
@@ -830,7 +896,7 @@ public:
     std::vector<uint32_t> anchor_flags_h;
     static constexpr int kAgain = -6; // PM_EAGAIN: the resident route does not apply; the caller takes the host route
 
-    void begin_store_call() { timing.clear(); last_events = last_rest = last_positions = last_candidates = last_accepted = last_grouped = last_grouped_wide = last_wide_regions = 0; last_handed_back = -1; last_alg[0] = last_alg[1] = last_alg[2] = 0; }      // (counts of the last search travel with pm_last_timing)
+    void begin_store_call() { timing.clear(); last_events = last_rest = last_positions = last_candidates = last_accepted = last_grouped = last_grouped_wide = last_wide_regions = 0; last_handed_back = -1; last_index_bucketed = last_index_overflow = 0; last_index_lost = -1; last_alg[0] = last_alg[1] = last_alg[2] = 0; }      // (counts of the last search travel with pm_last_timing)
     Store store_view() { return Store{d_anchor_start.p, d_ms_strand.p, d_anchor_lon.p, d_anchor_flags.p, d_ms_shift.p, d_ms_len.p, d_ms_state.p, ngen}; }
     // coherent: the reader must see marks made while its kernel runs (a wavefront that validates candidates in order)
     Layout layout_view(uint64_t* image, bool coherent = true) { return Layout{image, d_lay_off.p, d_lay_bits.p, coherent ? 1 : 0}; }
@@ -1559,6 +1625,11 @@ public:
     int filter_factor = 8;                // presence-filter bits per reference position, before rounding up to a power of two
     int slot_factor = 2;                  // index slots per reference position, before rounding up to a power of two (a measurement switch)
     bool bucket_sort = true;              // the events put in order by (pair, 256-position block) buckets (EventBucketCount ... CoarseFromBuckets); false: gathered and radix-sorted
+    bool index_build = true;              // the index of a region with index_bucket_min slots or more built by buckets in LDS (index_kernels.h); false: IndexInsert for every region
+    int64_t index_bucket_min = 1 << 24;   // ... slots of the smallest table built that way: the one shape it was measured faster at (a 5 Mb reference); a smaller table pays ~8 launches where IndexInsert's atomic rate is no problem
+    bool index_verify = false;            // (tests) IndexVerify after the build: pm_last_timing "index_lost"
+    int64_t index_overflow_cap = 0;       // (tests) capacity of the bucket build's overflow list (0: a 32nd of the bucketed positions + 1024)
+    int64_t last_index_bucketed = 0, last_index_overflow = 0, last_index_lost = -1;      // positions built by buckets, their overflow records, IndexVerify's violations (-1: not run)
     bool master_seg = true;               // Master.EP from the genomes' segments (MasterEPSeg); false: every lane against every staged event (MasterEP)
     bool force_gate = false;              // (tests) the second stage of a two-stage store_validate never runs
     int64_t chain_window = 4096;          // passed MUMs in a row that a window of store_chain_begin walks (diag_diff in bases); more: kChainWindow, the caller's list logic
@@ -1580,6 +1651,10 @@ public:
         if (key == "atomic_marks") { force_atomic_marks = value != 0; return true; }
         if (key == "master_seg") { master_seg = value != 0; return true; }
         if (key == "bucket_sort") { bucket_sort = value != 0; return true; }
+        if (key == "index_build") { index_build = value != 0; return true; }
+        if (key == "index_bucket_min" && value >= 1) { index_bucket_min = value; return true; }
+        if (key == "index_verify") { index_verify = value != 0; return true; }
+        if (key == "index_overflow_cap" && value >= 0) { index_overflow_cap = value; return true; }
         if (key == "filter_factor") { filter_factor = value < 1 ? 1 : (int)value; return true; }
         if (key == "slot_factor") { slot_factor = value < 1 ? 1 : (int)value; return true; }
         if (key == "stage_gate") { force_gate = value != 0; return true; }
@@ -1651,6 +1726,9 @@ private:
     template <class T> static void flush_on(T&, long) {}
     template <class T> static auto tune_copy_kernel(T& b, bool on, int) -> decltype(b.group_copies = on, true) { b.group_copies = on; return true; }
     template <class T> static bool tune_copy_kernel(T&, bool, long) { return true; }
+    // keys ordered by the bits [lo, hi) (stable), where the backend has the operation (HipBackend::sort_keys: rocprim::radix_sort_keys)
+    template <class T> static auto sort_keys_on(T& b, uint64_t* ki, uint64_t* ko, size_t n, int lo, int hi, int) -> decltype(b.sort_keys(ki, ko, n, lo, hi), true) { b.sort_keys(ki, ko, n, lo, hi); return true; }
+    template <class T> static bool sort_keys_on(T&, uint64_t*, uint64_t*, size_t, int, int, long) { return false; }
     void group_downloads() { group_on(be, 0); }
     void flush_downloads() { flush_on(be, 0); }
 
@@ -1664,6 +1742,7 @@ private:
     std::vector<CallHint> call_hints;
     int64_t call_ordinal = 0;      // candidates / accepted rows of the last call of a shape ([1]: one region = an anchor call): capacities of the next one's tail
     Buf<uint8_t> d_gflag; Buf<int64_t> d_glo;
+    Buf<int64_t> d_bkbase, d_bkbegin, d_ovf; Buf<uint64_t> d_ikey, d_ikey2, d_ikey3, d_ikey4;      // the bucket build of the index: first bucket per region, first record per bucket, overflow list, keys
     Buf<RegionInfo> d_R; Buf<int64_t> d_starts, d_lens, d_posbase;
     Buf<uint64_t> d_slots; Buf<uint32_t> d_filter, d_repeated; Buf<int32_t> d_next, d_rep, d_run, d_epm;
     Buf<int64_t> d_ucount, d_uoff; Buf<UnitRec> d_units;

@@ -439,6 +439,14 @@ struct HipBackend {
         check(rocprim::radix_sort_pairs(tmp, bytes, ki, ko, vi, vo, n, 0, (unsigned)bits, stream), "radix_sort_pairs");
     }
 
+    // keys only, ordered by the bits [begin_bit, end_bit) (stable): the index build's records by bucket
+    void sort_keys(uint64_t* ki, uint64_t* ko, size_t n, int begin_bit, int end_bit) {
+        size_t bytes = 0;
+        check(rocprim::radix_sort_keys(nullptr, bytes, ki, ko, n, (unsigned)begin_bit, (unsigned)end_bit, stream), "sort size");
+        need_tmp(bytes);
+        check(rocprim::radix_sort_keys(tmp, bytes, ki, ko, n, (unsigned)begin_bit, (unsigned)end_bit, stream), "radix_sort_keys");
+    }
+
     // phase timing: mark(name) opens a phase, mark(nullptr) closes the last one
     bool timing_on = true;      // pm_session_tune(s, "timing", 0): no events, collect() only waits for the stream
     void mark(const char* name) {

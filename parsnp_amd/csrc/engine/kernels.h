@@ -220,8 +220,12 @@ struct RegionInfo {        // one per region of a batch
     int64_t posbase;       // start of this region in the per-reference-position arrays
     int64_t fbase;         // first uint32 word of this region's presence filter
     uint32_t fmask;        // filter bits - 1 (power of two, >= 8 nR): one hashed bit per K-mer of the reference substring
-    uint32_t pad_;
+    uint32_t pad_;         // [5:0] sb, [13:8] fb, [16] built by buckets (index_kernels.h): a bucket is 2^sb consecutive slots and owns 2^fb
+                           // consecutive filter bits; a region that is not bucketed is one bucket (sb = log2 slots, fb = log2 filter bits)
 };
+constexpr uint32_t kBucketed = 1u << 16;
+PM_HD uint32_t region_sb(const RegionInfo& ri) { return ri.pad_ & 63u; }
+PM_HD uint32_t region_fb(const RegionInfo& ri) { return (ri.pad_ >> 8) & 63u; }
 
 constexpr uint64_t kEmpty = ~0ull;
 #ifndef PM_PER
@@ -439,6 +443,13 @@ PM_HD int32_t slot_head(uint64_t s) { return (int32_t)(s & 0x7fffffffu); }
 
 // the two filter bits of a K-mer inside its filter word (the second from hash bits the word index does not use)
 PM_HD uint32_t filter_mask(uint64_t hv, uint32_t bit) { return (1u << (bit & 31)) | (1u << ((uint32_t)(hv >> 58) & 31)); }
+// the filter bit of a K-mer with hash hv and home slot h: its bucket's piece of the filter (h >> sb), and in it fb hashed bits.  The
+// one place that says so: IndexInsert, the bucket build, index_lookup, index_probe and SeedExtend's own filter test all call it.
+// (One bucket: the high part is 0 and fb = log2 of the filter's bits -- the (hv >> 35) & fmask of the regions that are not bucketed.)
+PM_HD uint32_t filter_bit(const RegionInfo& ri, uint64_t hv, uint32_t h) {
+    const uint32_t fb = region_fb(ri);
+    return ((uint32_t)((uint64_t)h >> region_sb(ri)) << fb) | ((uint32_t)(hv >> 35) & ((1u << fb) - 1u));
+}
 
 // tid = flat reference position over the batch.
 struct IndexInsert {
@@ -450,6 +461,7 @@ struct IndexInsert {
         int64_t r = upper_slot(posbase, nregions, tid);
         const RegionInfo& ri = R[r];
         int32_t l = (int32_t)(tid - ri.posbase);
+        if (ri.pad_ & kBucketed) return;      // (built by buckets: index_kernels.h)
         next[tid] = -1;
         if (l + ri.K > ri.nR) { home[tid] = -1; return; }
         const int64_t base = P.goff[0] + ri.ref_pos;
@@ -460,7 +472,7 @@ struct IndexInsert {
         {   // presence filter: most query K-mers of a non-matching strand are rejected by one word that lives in L2.  Two
             // hashed bits of the SAME 32-bit word per K-mer (a blocked Bloom filter: still one load per probe): at 8 filter
             // bits per reference position a foreign K-mer passes with 5 % instead of the 12 % of one bit
-            const uint32_t bit = (uint32_t)(hv >> 35) & ri.fmask;
+            const uint32_t bit = filter_bit(ri, hv, h);
             atomic_or32(&filter[ri.fbase + (bit >> 5)], filter_mask(hv, bit));
         }
         for (;;) {
@@ -488,7 +500,7 @@ PM_HD uint64_t index_lookup(const Packed& P, const RegionInfo& ri, const uint64_
     const uint64_t fp = hv & 0xffffffff00000000ull;
     uint32_t h = (uint32_t)hv & ri.tmask;
     const int64_t base = P.goff[0] + ri.ref_pos;
-    const uint32_t bit = (uint32_t)(hv >> 35) & ri.fmask;
+    const uint32_t bit = filter_bit(ri, hv, h);
     { const uint32_t fm = filter_mask(hv, bit); if ((filter[ri.fbase + (bit >> 5)] & fm) != fm) return kEmpty; }
     for (;;) {
         const uint64_t seen = slots[ri.tbase + h];
@@ -504,7 +516,7 @@ PM_HD uint64_t index_probe(const RegionInfo& ri, const uint64_t* slots, const ui
     const uint64_t hv = hash_tag(tag);
     const uint64_t fp = hv & 0xffffffff00000000ull;
     uint32_t h = (uint32_t)hv & ri.tmask;
-    const uint32_t bit = (uint32_t)(hv >> 35) & ri.fmask;
+    const uint32_t bit = filter_bit(ri, hv, h);
     { const uint32_t fm = filter_mask(hv, bit); if ((filter[ri.fbase + (bit >> 5)] & fm) != fm) return kEmpty; }
     for (;;) {
         const uint64_t seen = slots[ri.tbase + h];
@@ -895,7 +907,7 @@ struct SeedExtend {
                 if (follow && u == 0 && sub == 0) go = slot != kEmpty;
                 else {
                     const uint64_t hv = hash_tag(ctag_at(u));
-                    const uint32_t bit = (uint32_t)(hv >> 35) & ri.fmask;
+                    const uint32_t bit = filter_bit(ri, hv, (uint32_t)hv & ri.tmask);
                     const uint32_t fm = filter_mask(hv, bit);
                     go = (filter[ri.fbase + (bit >> 5)] & fm) == fm;
                 }

@@ -364,7 +364,7 @@ void Aligner::collect_engine_timing() {
             if (!strcmp(names[i], "call_wall")) wall = ms[i];
             else if (strncmp(names[i], "alg_", 4) && strncmp(names[i], "n_", 2) && strcmp(names[i], "events") && strcmp(names[i], "rest_samples") && strcmp(names[i], "budget_retries") &&
                      strcmp(names[i], "exact_cluster_tests") && strcmp(names[i], "deferred_regions") && strcmp(names[i], "tail_repeats") && strcmp(names[i], "outside_writes") &&
-                     strcmp(names[i], "dense_regions") && strcmp(names[i], "dense_rounds") && strcmp(names[i], "dense_overrun")) dev += ms[i];
+                     strcmp(names[i], "dense_regions") && strcmp(names[i], "dense_rounds") && strcmp(names[i], "dense_overrun") && strncmp(names[i], "index_", 6)) dev += ms[i];
         }
         fprintf(stderr, "[engine call] wall %.3f ms, device phases %.3f ms\n", wall, dev);
     }
@@ -377,6 +377,8 @@ void Aligner::collect_engine_timing() {
         if (!strcmp(names[i], "n_grouped_wide")) { stats.grouped_wide += ms[i]; continue; }
         if (!strcmp(names[i], "n_wide_regions")) { stats.wide_regions += ms[i]; continue; }
         if (!strcmp(names[i], "n_handed_back")) { if (ms[i] > 0) stats.handed_back += ms[i]; continue; }
+        // (... and the counts of the index build by buckets: for callers of pm_last_timing, not for the phase tables)
+        if (!strncmp(names[i], "index_", 6)) continue;
         if (timing_first_call_) stats.anchor_ms.emplace_back(names[i], ms[i]);
         bool merged = false;
         for (auto& kv : stats.engine_ms) if (kv.first == names[i]) { kv.second += ms[i]; merged = true; }

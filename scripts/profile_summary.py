@@ -44,7 +44,7 @@ PHASES = {
     "compact": ["OkCount", "CompactCandidates", "CompactSp", "DirtyExtent", "DirtyPrefix", "DirtyMark", "DirtyMerge"],
     "settle": ["SettleClean", "StoreMarkOrdered", "StoreMark", "LayoutSentinel", "CollideMark", "CollideTest", "CollideClear", "CountTangled", "SettleFlagged", "SettleTangled",
                "TangleOwner", "TangleSettle", "TangleClear", "StoreInfoOut"],
-    "index": ["IndexInsert"],
+    "index": ["IndexInsert", "IndexKeys", "IndexBucketBounds", "IndexBucketFill", "IndexOverflow", "IndexVerify"],      # (the bucket build's radix sort of its keys shows under "sort": a rocPRIM kernel is counted once)
     "repeat": ["RunLength", "RepeatLength"],
     "seeds": ["ChainFlag", "AnchorList", "SeedCount", "SeedPlace", "SeedWalk"],
     "validate": ["ClustersDisjoint", "ClusterExtents", "ClusterInvolved", "ClusterDefer", "ReaderMark", "MarkerLook", "ReaderLook", "ClusterValidate", "OutsideWriteCheck", "StageGate"],
