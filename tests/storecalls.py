@@ -237,8 +237,12 @@ class Model:
 
     # ------------------------------------------------------------------ settle
     def settle(self):
+        return self.settle_rows(range(self.A))
+
+    def settle_rows(self, rows):
+        """setMums1's second half for the listed rows, in that order, against the marks as they are"""
         n = self.n
-        for c in range(self.A):
+        for c in rows:
             f, ln, sh = self.flags[c], self.lon[c], 0
             if (f & (ROW_BAD | ROW_OUTSIDE)) or ln < 5:
                 continue
