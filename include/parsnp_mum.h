@@ -327,6 +327,16 @@ int pm_store_rows(pm_session* s, const int32_t* rows, int64_t first, int64_t n, 
  * number of words; pm_store_layout copies it out */
 int64_t pm_store_layout_words(pm_session* s, int64_t* word_off);
 int pm_store_layout(pm_session* s, uint64_t* out, int64_t words);
+/* The unaligned runs of the layout, for parsnp.unalign (Aligner::setUnalignableRegions, src/parsnp.cpp:2310-2381), without the
+ * image leaving the device.  A run of genome j is a maximal stretch of unmarked bits in [0, n_j + 1) of its slice of the image;
+ * it is kept when it has at least 2 bases; its ordinal is its index among ALL runs of its genome, the one-base runs included.
+ * pm_store_unalign_count: per genome the number of all runs and of the kept ones (one wait).  pm_store_unalign_runs: start,
+ * end (inclusive) and ordinal of every kept run, genome after genome and in position order inside a genome, into arrays of n =
+ * the sum of kept_runs entries each (a different n is an error: the layout has changed since the count).  Valid where
+ * pm_store_layout is, sharded sessions included; both read the image and change nothing.  Phases `unalign_count` and
+ * `unalign_write` in pm_last_timing. */
+int pm_store_unalign_count(pm_session* s, int64_t* all_runs, int64_t* kept_runs);
+int pm_store_unalign_runs(pm_session* s, int32_t* start, int32_t* end, int32_t* ordinal, int64_t n);
 /* bytes this session has moved over the host link so far (every copy the engine issued, both directions) */
 int pm_session_traffic(const pm_session* s, uint64_t* h2d_bytes, uint64_t* d2h_bytes);
 

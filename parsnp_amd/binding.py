@@ -145,6 +145,25 @@ class Session:
         self.lib._check(self.lib.L.pm_store_chain_passed(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def unaligned_runs(self):
+        """pm_store_unalign_count + pm_store_unalign_runs: what parsnp.unalign lists, from the layout on the device -> (runs, all_runs,
+        kept_runs): runs[j] = (start, end, ordinal) of the kept runs of genome j (int32 arrays; end inclusive; ordinal among all runs
+        of the genome, the one-base runs included), all_runs[j] / kept_runs[j] the counts (int64)"""
+        L = self.lib.L
+        if not hasattr(L, "pm_store_unalign_count"):
+            raise PmError("this provider of the ABI has no pm_store_unalign_count")
+        v = C.c_void_p
+        L.pm_store_unalign_count.argtypes = [v, v, v]
+        L.pm_store_unalign_runs.argtypes = [v, v, v, v, C.c_int64]
+        ptr = lambda a: a.ctypes.data_as(v)      # noqa: E731
+        all_runs, kept = np.zeros(self.n, np.int64), np.zeros(self.n, np.int64)
+        self.lib._check(L.pm_store_unalign_count(self.h, ptr(all_runs), ptr(kept)))
+        total = int(kept.sum())
+        start, end, ordinal = (np.zeros(total, np.int32) for _ in range(3))
+        self.lib._check(L.pm_store_unalign_runs(self.h, ptr(start), ptr(end), ptr(ordinal), total))
+        at = np.concatenate([[0], np.cumsum(kept)])
+        return [(start[at[j]:at[j + 1]], end[at[j]:at[j + 1]], ordinal[at[j]:at[j + 1]]) for j in range(self.n)], all_runs, kept
+
     def __enter__(self):
         return self
 

@@ -272,6 +272,14 @@ int pm_store_layout(pm_session* s, uint64_t* out, int64_t words) {
     if (!s || !out) return fail(PM_EINVAL, "bad argument");
     PM_STORE_CALL(s->engine->store_layout(out, words))
 }
+int pm_store_unalign_count(pm_session* s, int64_t* all_runs, int64_t* kept_runs) {
+    if (!s || !all_runs || !kept_runs) return fail(PM_EINVAL, "bad argument");
+    PM_STORE_CALL(s->engine->store_unalign_count(all_runs, kept_runs))
+}
+int pm_store_unalign_runs(pm_session* s, int32_t* start, int32_t* end, int32_t* ordinal, int64_t n) {
+    if (!s || n < 0 || n >= ((int64_t)1 << 31) || (n > 0 && (!start || !end || !ordinal))) return fail(PM_EINVAL, "bad argument");
+    PM_STORE_CALL(s->engine->store_unalign_write(start, end, ordinal, n))
+}
 int pm_session_traffic(const pm_session* s, uint64_t* h2d_bytes, uint64_t* d2h_bytes) {
     if (!s) return PM_EINVAL;
     if (h2d_bytes) *h2d_bytes = s->backend->bytes_h2d;

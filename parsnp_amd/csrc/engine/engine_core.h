@@ -1543,6 +1543,66 @@ public:
         return 0;
     }
     std::vector<int64_t> lay_off_h;
+    // The unaligned runs of the layout (store_kernels.h, "the unaligned runs"): what parsnp.unalign lists, without the image
+    // leaving the device.  Both calls read the image and change nothing in it.
+    // the count pass and its scans, queued: per block the runs, kept starts and kept ends before it; per genome the totals
+    int64_t unalign_launch() {
+        const size_t ngz = (size_t)ngen;
+        layout_geometry();
+        if (un_blk_h.size() != ngz + 1) {
+            un_blk_h.assign(ngz + 1, 0);
+            for (size_t j = 0; j < ngz; j++) un_blk_h[j + 1] = un_blk_h[j] + ((glen_h[j] + 1 + 63) / 64 + kUnalignWords - 1) / kUnalignWords;
+            ensure(d_un_blk, ngz + 1);
+            be.h2d(d_un_blk.p, un_blk_h.data(), 8 * (ngz + 1));
+        }
+        const int64_t nblocks = un_blk_h[ngz];
+        ensure(d_un_cnt, 3 * ((size_t)nblocks + 1)); ensure(d_un_scan, 3 * ((size_t)nblocks + 1)); ensure(d_un_tot, 2 * ngz);
+        const size_t row = (size_t)nblocks + 1;
+        be.launch_wave("unalign_count", nblocks, UnalignCount{unalign_geom(), nblocks, d_un_cnt.p, d_un_cnt.p + row, d_un_cnt.p + 2 * row});
+        for (size_t k = 0; k < 3; k++) be.exclusive_scan(d_un_cnt.p + k * row, d_un_scan.p + k * row, row);
+        be.launch("unalign_totals", (int64_t)ngen, UnalignTotals{d_un_blk.p, d_un_scan.p, d_un_scan.p + row, d_un_tot.p});
+        return nblocks;
+    }
+    UnalignGeom unalign_geom() {
+        int32_t steps = 0;
+        while (((int64_t)1 << steps) < ngen) steps++;
+        return UnalignGeom{d_image.p, d_lay_off.p, d_lay_bits.p, d_un_blk.p, ngen, steps};
+    }
+    // per genome: the number of all runs and of the kept ones (the call's one wait)
+    int store_unalign_count(int64_t* all_runs, int64_t* kept_runs) {
+        if (!resident || layout_rows < 0) { error = "the anchor list has not been settled"; return -2; }
+        begin_store_call();
+        be.mark("unalign_count");
+        unalign_launch();
+        be.mark(nullptr);
+        std::vector<int64_t> tot(2 * (size_t)ngen);
+        be.d2h(tot.data(), d_un_tot.p, 8 * tot.size());
+        for (size_t j = 0; j < (size_t)ngen; j++) { all_runs[j] = tot[2 * j]; kept_runs[j] = tot[2 * j + 1]; }
+        collect_timing_more();
+        return 0;
+    }
+    // start, end (inclusive) and ordinal of every kept run, genome after genome, in position order: n = the sum of the kept counts.
+    // The counts are taken again (the image may have changed since the count call: the sum is checked after the one wait, and a
+    // rank past n is never written)
+    int store_unalign_write(int32_t* start, int32_t* end, int32_t* ordinal, int64_t n) {
+        if (!resident || layout_rows < 0) { error = "the anchor list has not been settled"; return -2; }
+        begin_store_call();
+        be.mark("unalign_write");
+        const int64_t nblocks = unalign_launch();
+        const size_t row = (size_t)nblocks + 1, nz = (size_t)n;
+        ensure(d_un_out, 3 * std::max<size_t>(nz, 1));
+        be.launch_wave("unalign_write", nblocks, UnalignWrite{unalign_geom(), nblocks, d_un_scan.p, d_un_scan.p + row, d_un_scan.p + 2 * row, d_un_out.p, d_un_out.p + nz, d_un_out.p + 2 * nz, n});
+        be.mark(nullptr);
+        int64_t total[2] = {0, 0};      // kept starts, kept ends
+        be.d2h_async(&total[0], d_un_scan.p + row + nblocks, 8);
+        be.d2h_async(&total[1], d_un_scan.p + 2 * row + nblocks, 8);
+        if (n) { be.d2h_async(start, d_un_out.p, 4 * nz); be.d2h_async(end, d_un_out.p + nz, 4 * nz); be.d2h_async(ordinal, d_un_out.p + 2 * nz, 4 * nz); }
+        be.sync();
+        collect_timing_more();
+        if (total[0] != n || total[1] != n) { error = "the number of kept runs does not match the layout"; return -2; }
+        return 0;
+    }
+    std::vector<int64_t> un_blk_h;
 
     // The suffix array of the flagged regions of a batch (dense_kernels.h) and their rep' (after RepeatLength, which skipped them).
     // One segmented prefix-doubling sort over all of them; every round waits for its count of distinct ranks (8 bytes) -- a round
@@ -1762,6 +1822,7 @@ private:
     Buf<int32_t> d_anchor_start, d_anchor_lon; Buf<uint32_t> d_anchor_flags;      // the MUM store's rows as the searches delivered them
     int64_t table_counter = 0;
     Buf<uint64_t> d_image;
+    Buf<int64_t> d_un_blk, d_un_cnt, d_un_scan, d_un_tot; Buf<int32_t> d_un_out;      // the unaligned runs: block geometry, counts per block, their scans, totals per genome, the runs
     Buf<uint8_t> d_ms_strand, d_ms_state, d_small8, d_o_strand; Buf<int32_t> d_ms_shift, d_ms_len, d_list, d_list2, d_j_min, d_j_max, d_o_start;
     Buf<int64_t> d_rg_start, d_rg_len, d_lay_off, d_lay_bits, d_v_row0, d_v_first, d_f_start, d_f_end, d_f_pack; Buf<RegInfo> d_rg_info; Buf<uint64_t> d_rg_count, d_once, d_twice;
     Buf<RowInfo> d_rowinfo; Buf<uint64_t> d_alg;

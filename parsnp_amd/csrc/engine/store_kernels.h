@@ -2221,4 +2221,134 @@ struct StoreInfoOut {
     }
 };
 
+// ------------------------------------------------------------------------------------------ the unaligned runs
+// parsnp.unalign (Aligner::setUnalignableRegions, src/parsnp.cpp:2310-2381) lists, per genome, the maximal stretches of bases no
+// MUM covers: the complement of the layout.  A RUN is a maximal stretch of unmarked bits in [0, nbits) of a genome's slice of
+// the image (sentinel included: the host's walk tests that bit like every other); it is KEPT with at least 2 bases (the
+// reference skips a run whose start is its end), and its ORDINAL counts every run of its genome before it, the one-base runs
+// included (the reference's round-robin spends a round on those too).
+//
+// One wavefront takes a BLOCK of 64 consecutive image words of one genome, one lane per word, and looks at nothing but those
+// words and the one before and after them: z = ~word under the genome's valid bits, a run starts where z has a bit whose
+// lower neighbour is clear and ends where the upper neighbour is clear ("marked" outside the genome), and a bit that is both is
+// a one-base run.  The lanes exchange their z through 66 words of LDS (a neighbour's word is one ds_read; a lane shuffle has no
+// counterpart where one thread plays every lane) and the two words outside the block cost one extra load each.  No wavefront
+// waits for another: the count pass leaves three counts per block (all starts, kept starts, kept ends), rocPRIM scans them over
+// ALL blocks, and because the blocks lie genome after genome a genome's base is the scanned value at its first block.  The
+// write pass repeats the geometry and drops every kept start (with its ordinal) and every kept end at its rank: kept starts and
+// kept ends pair by rank, so slot i holds both ends of kept run i.  Plain stores, no atomics; every loop has a constant trip
+// count or one that is uniform over the wavefront.
+constexpr int kUnalignWords = 64;      // image words of a block
+struct UnalignGeom {
+    const uint64_t* image; const int64_t* word_off; const int64_t* nbits;
+    const int64_t* blk_off;      // [ngen + 1]: first block of every genome
+    int32_t ngen; int32_t steps; // steps: rounds of the search for a block's genome (2^steps > ngen)
+};
+// genome of block b: the last j with blk_off[j] <= b (genomes without a block -- none has: a genome holds its sentinel -- are passed over)
+PM_HD int32_t unalign_genome(const UnalignGeom& G, int64_t b) {
+    int32_t lo = 0, hi = G.ngen;      // blk_off[lo] <= b < blk_off[hi]
+    for (int s = 0; s < G.steps; s++) {
+        const int32_t mid = lo + ((hi - lo) >> 1);
+        if (mid > lo) { if (G.blk_off[mid] <= b) lo = mid; else hi = mid; }
+    }
+    return lo;
+}
+// unmarked valid bits of word i of a genome of nb bits; 0 outside it
+PM_HD uint64_t unalign_z(const uint64_t* w, int64_t nb, int64_t i) {
+    if (i < 0 || i * 64 >= nb) return 0;
+    const int64_t left = nb - i * 64;
+    return ~w[i] & (left >= 64 ? ~0ull : ((1ull << left) - 1));
+}
+// bits of z where a run starts / ends, given the words below and above
+PM_HD uint64_t unalign_starts(uint64_t z, uint64_t below) { return z & ~((z << 1) | (below >> 63)); }
+PM_HD uint64_t unalign_ends(uint64_t z, uint64_t above) { return z & ~((z >> 1) | (above << 63)); }
+// counts of a word, packed: all starts | kept starts << 16 | kept ends << 32 (a block has at most 32 * 64 of each)
+PM_HD uint64_t unalign_pack(uint64_t starts, uint64_t ends) {
+    return (uint64_t)__builtin_popcountll(starts) | ((uint64_t)__builtin_popcountll(starts & ~ends) << 16) | ((uint64_t)__builtin_popcountll(ends & ~starts) << 32);
+}
+struct UnalignCount {
+    UnalignGeom G; int64_t nblocks;
+    int64_t* n_all; int64_t* n_kstart; int64_t* n_kend;      // [nblocks + 1] each (the last entry 0: the scans' totals land there)
+    PM_HD void wave(int64_t b) const {
+        if (b >= nblocks) return;
+        const int32_t g = unalign_genome(G, b);
+        const uint64_t* w = G.image + G.word_off[g];
+        const int64_t nb = G.nbits[g];
+        const int64_t w0 = (b - G.blk_off[g]) * kUnalignWords;
+        PM_WAVE_SHARED uint64_t z[kUnalignWords + 2];      // z[t]: word w0 + t - 1
+        lanes_for(0, kUnalignWords + 2, [&](int t) { z[t] = unalign_z(w, nb, w0 + t - 1); });
+        wave_sync();
+        uint64_t acc = 0;
+        lanes_for(0, kUnalignWords, [&](int t) { acc += unalign_pack(unalign_starts(z[t + 1], z[t]), unalign_ends(z[t + 1], z[t + 2])); });
+        acc = wave_sum_u64(acc);
+        if (wave_leader()) {
+            n_all[b] = (int64_t)(acc & 0xffff); n_kstart[b] = (int64_t)((acc >> 16) & 0xffff); n_kend[b] = (int64_t)((acc >> 32) & 0xffff);
+            if (b == nblocks - 1) { n_all[nblocks] = 0; n_kstart[nblocks] = 0; n_kend[nblocks] = 0; }
+        }
+    }
+};
+// per genome: all runs, kept runs (from the scans: the value at the genome's first block is the count of everything before it)
+struct UnalignTotals {
+    const int64_t* blk_off; const int64_t* s_all; const int64_t* s_kstart; int64_t* out;      // out[2 j], out[2 j + 1]
+    PM_HD void operator()(int64_t j) const {
+        out[2 * j] = s_all[blk_off[j + 1]] - s_all[blk_off[j]];
+        out[2 * j + 1] = s_kstart[blk_off[j + 1]] - s_kstart[blk_off[j]];
+    }
+};
+struct UnalignWrite {
+    UnalignGeom G; int64_t nblocks;
+    const int64_t* s_all; const int64_t* s_kstart; const int64_t* s_kend;      // exclusive scans of UnalignCount's counts
+    int32_t* start; int32_t* end; int32_t* ordinal; int64_t cap;              // slots of the caller (a rank at or past cap is not written)
+    PM_HD void wave(int64_t b) const {
+        if (b >= nblocks) return;
+        const int32_t g = unalign_genome(G, b);
+        const uint64_t* w = G.image + G.word_off[g];
+        const int64_t nb = G.nbits[g];
+        const int64_t w0 = (b - G.blk_off[g]) * kUnalignWords;
+        PM_WAVE_SHARED uint64_t z[kUnalignWords + 2];
+        PM_WAVE_SHARED uint64_t part[2][kUnalignWords];
+        lanes_for(0, kUnalignWords + 2, [&](int t) { z[t] = unalign_z(w, nb, w0 + t - 1); });
+        wave_sync();
+        int32_t most = 0;      // the largest number of kept starts or kept ends of one word of the block: the trip count of the stores
+        lanes_for(0, kUnalignWords, [&](int t) {
+            const uint64_t p = unalign_pack(unalign_starts(z[t + 1], z[t]), unalign_ends(z[t + 1], z[t + 2]));
+            part[0][t] = p;
+            const int32_t a = (int32_t)((p >> 16) & 0xffff), e = (int32_t)((p >> 32) & 0xffff);
+            if (a > most) most = a;
+            if (e > most) most = e;
+        });
+        most = wave_max_i32(most);
+        wave_sync();
+        // inclusive prefix over the lanes (six doubling steps through LDS; the three counts ride in one word)
+        int cur = 0;
+        for (int d = 1; d < kUnalignWords; d <<= 1) {
+            lanes_for(0, kUnalignWords, [&](int t) { part[cur ^ 1][t] = part[cur][t] + (t >= d ? part[cur][t - d] : 0); });
+            wave_sync();
+            cur ^= 1;
+        }
+        const int64_t ord0 = s_all[b] - s_all[G.blk_off[g]];      // runs of this genome before the block
+        const int64_t ks0 = s_kstart[b], ke0 = s_kend[b];
+        lanes_for(0, kUnalignWords, [&](int t) {
+            const uint64_t before = t ? part[cur][t - 1] : 0;
+            const uint64_t st = unalign_starts(z[t + 1], z[t]), en = unalign_ends(z[t + 1], z[t + 2]);
+            uint64_t ks = st & ~en, ke = en & ~st;
+            int64_t rs = ks0 + (int64_t)((before >> 16) & 0xffff), re = ke0 + (int64_t)((before >> 32) & 0xffff);
+            const int64_t o0 = ord0 + (int64_t)(before & 0xffff);
+            const int64_t base = (w0 + t) * 64;
+            for (int32_t k = 0; k < most; k++) {
+                if (ks) {
+                    const int bit = ctz64(ks);
+                    if (rs < cap) { start[rs] = (int32_t)(base + bit); ordinal[rs] = (int32_t)(o0 + __builtin_popcountll(st & ((1ull << bit) - 1))); }
+                    rs++; ks &= ks - 1;
+                }
+                if (ke) {
+                    const int bit = ctz64(ke);
+                    if (re < cap) end[re] = (int32_t)(base + bit);
+                    re++; ke &= ke - 1;
+                }
+            }
+        });
+    }
+};
+
 }  // namespace pm

@@ -23,6 +23,7 @@
 #include <algorithm>
 #include <functional>
 #include <future>
+#include <iosfwd>
 #include <map>
 #include <memory>
 #include <string>
@@ -60,6 +61,15 @@ struct Genome {
 };
 // returns false when the file cannot be opened; *console receives what the reference prints to stdout for this file
 bool ingest(const std::string& path, bool is_ref, bool reverse, int d, Genome* out, std::string* console);
+
+// The runs of bases no MUM covers (parsnp.unalign): per genome the maximal stretches of unmarked bits of its layout, sentinel bit
+// included.  Kept are the runs of at least 2 bases, genome after genome in position order (genome k: [first[k], first[k + 1]));
+// the ordinal of a run counts ALL runs of its genome before it, the one-base runs included.
+struct UnalignRuns {
+    std::vector<int64_t> all, kept, first;
+    std::vector<int32_t> start, end, ordinal;      // end inclusive
+    double device_ms = 0, d2h_bytes = 0;           // kernel time of the engine's two calls and what they sent to the host (resident route)
+};
 
 // n+1 bits per genome, bit [n] is the sentinel (parsnp.cpp:3184-3185)
 class Bitmap {
@@ -142,6 +152,7 @@ public:
     long next_set(long from) const;     // smallest i >= from with bit set; the sentinel guarantees one for from <= n
     long prev_set(long from) const;     // largest i <= from with bit set, or -1
     size_t bits() const { return nbits_; }
+    const uint64_t* words() const { return w_; }      // (bits() + 63) / 64 of them hold the bits; the word-wise scan of parsnp.unalign reads them
     // undo log support (speculative replay): words changed since begin_log() are restored by rollback()
     void begin_log() { logging_ = true; log_.clear(); }
     bool logging() const { return logging_; }
@@ -345,7 +356,9 @@ public:
     bool resident_failed() const { return res_.failed; }
     const std::string& resident_why() const { return res_.why; }
     bool resident_chain();                               // phases C-D from the device (resident.cpp); false: the caller runs them
-    void materialize();                                  // rows of the LCBs' MUMs (and the layout, for parsnp.unalign) for the writer; no-op on the host route
+    void materialize();                                  // rows of the LCBs' MUMs for the writer; no-op on the host route
+    void unaligned_runs(UnalignRuns* out);               // the runs parsnp.unalign lists: from the device's layout on the resident route, from `layout` otherwise
+    void attach_layout_image();                          // resident route: the device's layout fetched into `layout` (the bit-by-bit checker of parsnp.unalign, a test hook)
     // After resident_chain() returned true `mums` and `lcbs` are NOT written yet: the device's answer is kept (Resident::chain_*)
     // and the step report reads its counts from summary().  final_mums() / final_lcbs() write the lists on first use; whoever
     // reads `mums` / `lcbs` of a finished run goes through them (or calls require_lists() where it takes the members directly).
@@ -382,7 +395,7 @@ private:
         std::vector<int64_t> found_key;                                        // pool[i] of the recursion: where its REGION stands in the reference's processing order (reference start, generation; -1: the first pushed seed)
         std::vector<pm_region_info> gen_info; std::vector<int32_t> gen_id;     // the seed regions, in push order
         std::vector<int32_t> fallback_start; std::vector<uint8_t> fallback_strand;   // rows fetched for the host route
-        std::vector<uint64_t> image;                                           // the layout, fetched for parsnp.unalign
+        std::vector<uint64_t> image;                                           // the layout, fetched for the checker of parsnp.unalign (attach_layout_image)
         std::vector<pm_row_info> anchor_info; size_t anchor_rows = 0; const int32_t* anchor_lon = nullptr; long anchor_slength = 0; size_t anchor_accepted = 0;   // what resident_records() writes the anchors' MUM records from
         bool records_done = true;
         std::vector<int32_t> of_row, len_of_row;      // store row -> index of its MUM record in the pool (-1: none), and its length
@@ -480,8 +493,18 @@ struct GapCounts {
 extern GapCounts gap_counts;
 // XMFA + log (writeOutput).  gap_note: set when the gap aligner (gapalign.h) declined an inter-MUM gap and it was written '-'-padded.
 void write_output(Aligner& a, const std::string& stem, bool* gap_note);
-// parsnp.unalign (setUnalignableRegions); marks every base of the layout bitmaps.
+// parsnp.unalign (setUnalignableRegions): the runs (Aligner::unaligned_runs), then the records; the layout is read, not written.
 void write_unaligned(Aligner& a);
+// the records of parsnp.unalign from the runs, in the reference's round-robin order, formatted on `threads` threads
+void write_unaligned_records(const UnalignRuns& runs, const std::vector<Genome>& genomes, int threads, std::ostream& out);
+// one record: header line, end - start bases in lines of 80, "=" (the quirks: write_unaligned)
+void append_unaligned_record(std::string& rec, size_t k, long startpos, long endpos, const Genome& gn);
+// the runs of unmarked bits in [0, nbits) of one genome's bitmap words, word by word: appends start / end / ordinal of the kept ones
+// (at least 2 bases), returns the number of all runs
+int64_t scan_unaligned_words(const uint64_t* w, int64_t nbits, std::vector<int32_t>* start, std::vector<int32_t>* end, std::vector<int32_t>* ordinal);
+// what the last write_unaligned did (PARSNP_TIMING: unalign_*)
+struct UnalignCounts { double s = 0; long runs = 0, kept = 0; double device_ms = 0, d2h_bytes = 0; };
+extern UnalignCounts unalign_counts;
 
 std::string reverse_complement(const std::string& s);   // Aligner::reversec, :1294-1393
 

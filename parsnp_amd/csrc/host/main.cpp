@@ -134,6 +134,10 @@ int main(int argc, char* argv[]) {
     if (const char* tf = getenv("PARSNP_TIMING")) {
         FILE* f = fopen(tf, "w");
         if (f) {
+            uint64_t session_d2h = 0;       // everything the engine sent to the host in this process, the writer's downloads included
+            (void)pm_session_traffic(run.session, nullptr, &session_d2h);
+            double layout_bytes = 0;        // size of the engine's layout image: a bit per base and a sentinel, whole words and one spare per genome
+            for (const auto& g : run.genomes) layout_bytes += 8.0 * (double)((g.seq.size() + 1 + 63) / 64 + 1);
             double outside_writes = 0;      // accepted reverse-strand members outside their region that stayed on the resident route
             double dense_regions = 0;       // regions of the run's searches that took the suffix-array path (their walks ran out of budget)
             for (const auto& kv : rep.host.engine_ms) { if (kv.first == "outside_writes") outside_writes = kv.second; if (kv.first == "dense_regions") dense_regions = kv.second; }
@@ -147,7 +151,8 @@ int main(int argc, char* argv[]) {
                     "\"gap_note\": %s, \"tie_fallbacks\": %ld, \"literal_iterations\": %ld, \"parallel_candidates\": %ld, \"parallel_dirty\": %ld, \"t_validate\": %.6f, \"t_neighbour\": %.6f, \"t_sweep\": %.6f, \"t_replay\": %.6f, \"t_key\": %.6f, \"resident\": %ld, \"resident_retry\": %ld, \"device_chain\": %ld, \"chain_passed\": %ld, \"h2d_bytes\": %.0f, \"d2h_bytes\": %.0f, \"outside_writes\": %.0f, \"dense_regions\": %.0f, \"resident_why\": \"%s\", "
                     "\"gap_jobs\": %ld, \"gap_jobs_wide\": %ld, \"gap_longest\": %ld, \"gap_device_narrow\": %ld, \"gap_device_wide\": %ld, \"gap_host\": %ld, \"gap_host_s\": %.6f, "
                     "\"gap_device_narrow_ms\": %.3f, \"gap_device_wide_ms\": %.3f, \"gap_device_tall\": %ld, \"gap_device_tall_ms\": %.3f, "
-                    "\"gap_jobs_long\": %ld, \"gap_device_long\": %ld, \"gap_device_long_ms\": %.3f, \"gap_device_long_tall\": %ld, \"gap_device_long_tall_ms\": %.3f}\n",
+                    "\"gap_jobs_long\": %ld, \"gap_device_long\": %ld, \"gap_device_long_ms\": %.3f, \"gap_device_long_tall\": %ld, \"gap_device_long_tall_ms\": %.3f, "
+                    "\"unalign_s\": %.6f, \"unalign_runs\": %ld, \"unalign_kept\": %ld, \"unalign_device_ms\": %.3f, \"unalign_d2h_bytes\": %.0f, \"session_d2h_bytes\": %.0f, \"layout_bytes\": %.0f}\n",
                     pm_provider(), run.genomes.size(), run.qfiles, run.ingest_s, run.upload_s, rep.path_s, rep.anchor_s, rep.extend_s, rep.filter_s,
                     rep.lcb_s, output_s, now_s() - t_begin, rep.finder_s, rep.finder_calls, rep.finder_regions, rep.regions_processed,
                     rep.cache_hits, rep.cache_misses, rep.spec_rounds, rep.anchors, rep.mums, rep.lcbs, rep.core_bp, gap_note ? "true" : "false",
@@ -155,7 +160,8 @@ int main(int argc, char* argv[]) {
                     rep.host.resident, rep.host.resident_retry, rep.host.device_chain, rep.host.chain_passed, rep.h2d_bytes, rep.d2h_bytes, outside_writes, dense_regions, why.c_str(),
                     gap_counts.jobs, gap_counts.jobs_wide, gap_counts.longest, gap_counts.device_narrow, gap_counts.device_wide, gap_counts.host, gap_counts.host_s,
                     gap_counts.device_narrow_ms, gap_counts.device_wide_ms, gap_counts.device_tall, gap_counts.device_tall_ms,
-                    gap_counts.jobs_long, gap_counts.device_long, gap_counts.device_long_ms, gap_counts.device_long_tall, gap_counts.device_long_tall_ms);
+                    gap_counts.jobs_long, gap_counts.device_long, gap_counts.device_long_ms, gap_counts.device_long_tall, gap_counts.device_long_tall_ms,
+                    unalign_counts.s, unalign_counts.runs, unalign_counts.kept, unalign_counts.device_ms, unalign_counts.d2h_bytes, (double)session_d2h, layout_bytes);
             fclose(f);
         }
     }

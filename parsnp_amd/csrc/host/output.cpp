@@ -945,9 +945,20 @@ void write_output(Aligner& a, const std::string& stem, bool* gap_note) {
 // emitting the next run of bases no MUM covers.  Quirks kept: the record holds end-start bases (the last base of the run is
 // dropped), runs of one base are skipped, a trailing single character of the 80-column wrap is not printed, and the
 // coordinates are 0-based positions of the padded in-memory genome.
-void write_unaligned(Aligner& a) {
-    a.require_lists("write_unaligned");
+//
+// The reference walks the layout bit by bit, marking every run it has printed so that the next round finds the next one.  Here
+// the work is split: THE RUNS (Aligner::unaligned_runs: per genome every maximal stretch of unmarked bits, the kept ones -- at
+// least 2 bases -- with their index among all runs of the genome) and THE RECORDS.  Round r of the reference's loop emits run r
+// of every genome that has one and keeps it (a one-base run costs its genome the round), and the loop ends after the first
+// round in which the LAST genome has no run left, so the file is
+//     { (r, k) : r < runs[k], r <= runs[n - 1], run r of genome k is kept }   in the order of (r, k).
+// (the scan of a bitmap's words and the records: unalign.cpp)
+#if defined(PARSNP_TEST_HOOKS)
+namespace {
+// the reference's walk, bit by bit and marking as it goes: the checker of the writer above (test hook PARSNP_UNALIGN_WALK)
+void walk_unaligned(Aligner& a) {
     using namespace std;
+    a.attach_layout_image();
     a.wait_layout();
     const size_t n = a.n;
     ofstream out((a.prm.outdir + "/parsnp.unalign").c_str());
@@ -974,16 +985,7 @@ void write_unaligned(Aligner& a) {
             }
             if (startpos != endpos) {
                 rec.clear();
-                rec += ">" + to_string(k + 1) + ":" + to_string(startpos) + "-" + to_string(endpos) + " + " + a.genomes[k].fname + "\n";
-                const string& g = a.genomes[k].seq;
-                const size_t len = (size_t)(endpos - startpos);
-                const size_t from = (size_t)startpos;
-                const size_t avail = from <= g.size() ? min(len, g.size() - from) : 0;
-                size_t pos = 0;
-                while (pos + 80 < avail) { rec.append(g, from + pos, 80); rec.push_back('\n'); pos += 80; }
-                if (pos + 1 < avail) { rec.append(g, from + pos, avail - pos); rec.push_back('\n'); }
-                if (avail == 0) rec += "-\n";
-                rec += "=\n";
+                append_unaligned_record(rec, k, startpos, endpos, a.genomes[k]);
                 out.write(rec.data(), (streamsize)rec.size());
             } else if (startpos == -1 && k == n - 1) {
                 stop = true;
@@ -991,6 +993,26 @@ void write_unaligned(Aligner& a) {
         }
     }
     out.close();
+}
+}  // namespace
+#endif
+
+void write_unaligned(Aligner& a) {
+    a.require_lists("write_unaligned");
+    using namespace std;
+    const auto t0 = chrono::steady_clock::now();
+    unalign_counts = UnalignCounts();
+#if defined(PARSNP_TEST_HOOKS)
+    if (test_hook("PARSNP_UNALIGN_WALK")) { walk_unaligned(a); unalign_counts.s = chrono::duration<double>(chrono::steady_clock::now() - t0).count(); return; }
+#endif
+    UnalignRuns runs;
+    a.unaligned_runs(&runs);
+    ofstream out((a.prm.outdir + "/parsnp.unalign").c_str());
+    write_unaligned_records(runs, a.genomes, a.prm.cores > 0 ? a.prm.cores : 1, out);
+    out.close();
+    for (size_t k = 0; k < a.n; k++) { unalign_counts.runs += (long)runs.all[k]; unalign_counts.kept += (long)runs.kept[k]; }
+    unalign_counts.device_ms = runs.device_ms; unalign_counts.d2h_bytes = runs.d2h_bytes;
+    unalign_counts.s = chrono::duration<double>(chrono::steady_clock::now() - t0).count();
 }
 
 }  // namespace parsnp

@@ -27,6 +27,9 @@
 // (an entry point a provider may lack -- the CPU checker's: the search then runs alone and the work beside it after it)
 extern "C" int pm_store_search_beside(pm_session* s, const int32_t* regions, const int32_t* minsize, int64_t n, int64_t* first_row, int64_t* offsets,
                                       void (*beside)(void*), void* ctx) __attribute__((weak));
+// (likewise: the CPU checker has no store, and no resident route on which these would be called)
+extern "C" int pm_store_unalign_count(pm_session* s, int64_t* all_runs, int64_t* kept_runs) __attribute__((weak));
+extern "C" int pm_store_unalign_runs(pm_session* s, int32_t* start, int32_t* end, int32_t* ordinal, int64_t n) __attribute__((weak));
 
 namespace parsnp {
 
@@ -671,8 +674,7 @@ void Aligner::resident_fill_between() {
     lcbs.insert(lcbs.begin(), fillers.begin(), fillers.end());
 }
 
-// The rows the XMFA writer reads -- every MUM of an LCB, the LCBs' own start / end rows -- and, for parsnp.unalign, the
-// layout: fetched once, after phase D.
+// The rows the XMFA writer reads -- every MUM of an LCB, the LCBs' own start / end rows: fetched once, after phase D.
 void Aligner::materialize() {
     if (!res_.active || res_.materialized) return;
     res_.materialized = true;
@@ -714,15 +716,64 @@ void Aligner::materialize() {
         c.end.resize(n);
         for (size_t k = 0; k < n; k++) c.end[k] = b.end(k);
     }
-    if (prm.unaligned) {      // write_unaligned walks (and marks) the layout
-        wait_layout();
-        std::vector<int64_t> off(n + 1);
-        const int64_t words = pm_store_layout_words(session_, off.data());
-        res_.image.resize((size_t)words);
-        if (pm_store_layout(session_, res_.image.data(), words) != PM_OK) engine_error("cannot fetch the layout", PM_EHIP);
-        for (size_t j = 0; j < n; j++) layout[j].attach(res_.image.data() + off[j], (size_t)(off[j + 1] - off[j]), genomes[j].seq.size() + 1);
-    }
+    // (the layout stays where it is: parsnp.unalign takes its runs from the device, unaligned_runs())
     if (getenv("PARSNP_DEBUG_TIMERS")) fprintf(stderr, "[resident] rows of %zu MUMs fetched for the writer %.4f s\n", rows.size(), now_s() - t0);
+}
+
+// The device's layout as the host's bitmaps: only the bit-by-bit checker of parsnp.unalign asks for it (a test hook).
+void Aligner::attach_layout_image() {
+    if (!res_.active) return;
+    wait_layout();
+    std::vector<int64_t> off(n + 1);
+    const int64_t words = pm_store_layout_words(session_, off.data());
+    res_.image.resize((size_t)words);
+    if (pm_store_layout(session_, res_.image.data(), words) != PM_OK) engine_error("cannot fetch the layout", PM_EHIP);
+    for (size_t j = 0; j < n; j++) layout[j].attach(res_.image.data() + off[j], (size_t)(off[j + 1] - off[j]), genomes[j].seq.size() + 1);
+}
+
+// The runs parsnp.unalign lists.  Resident route: counted and listed by the engine from the layout on the device (12 bytes per
+// kept run come to the host instead of one bit per base).  Host route: a word-wise scan of the bitmaps, a thread per genome.
+void Aligner::unaligned_runs(UnalignRuns* out) {
+    out->all.assign(n, 0); out->kept.assign(n, 0); out->first.assign(n + 1, 0);
+    out->device_ms = 0; out->d2h_bytes = 0;
+    if (res_.active) {
+        if (!pm_store_unalign_count || !pm_store_unalign_runs) fatal("this provider of the engine's ABI cannot list the unaligned runs");
+        auto device_ms = [&](const char* phase) {
+            int cnt = 64; const char* names[64]; float ms[64];
+            if (pm_last_timing(session_, &cnt, names, ms) != PM_OK) return;
+            for (int i = 0; i < cnt; i++) if (!strcmp(names[i], phase)) out->device_ms += ms[i];
+        };
+        uint64_t d0 = 0, d1 = 0;
+        (void)pm_session_traffic(session_, nullptr, &d0);
+        int rc = pm_store_unalign_count(session_, out->all.data(), out->kept.data());
+        if (rc != PM_OK) engine_error("cannot count the unaligned runs", rc);
+        device_ms("unalign_count");
+        for (size_t k = 0; k < n; k++) out->first[k + 1] = out->first[k] + out->kept[k];
+        const size_t total = (size_t)out->first[n];
+        out->start.resize(total); out->end.resize(total); out->ordinal.resize(total);
+        rc = pm_store_unalign_runs(session_, out->start.data(), out->end.data(), out->ordinal.data(), (int64_t)total);
+        if (rc != PM_OK) engine_error("cannot list the unaligned runs", rc);
+        device_ms("unalign_write");
+        (void)pm_session_traffic(session_, nullptr, &d1);
+        out->d2h_bytes = (double)(d1 - d0);
+        return;
+    }
+    wait_layout();
+    std::vector<std::vector<int32_t>> st(n), en(n), ord(n);
+    const int threads = prm.cores > 0 ? prm.cores : 1;
+#pragma omp parallel for schedule(dynamic, 1) num_threads(threads)
+    for (long k = 0; k < (long)n; k++) {
+        out->all[(size_t)k] = scan_unaligned_words(layout[(size_t)k].words(), (int64_t)layout[(size_t)k].bits(), &st[(size_t)k], &en[(size_t)k], &ord[(size_t)k]);
+        out->kept[(size_t)k] = (int64_t)st[(size_t)k].size();
+    }
+    for (size_t k = 0; k < n; k++) out->first[k + 1] = out->first[k] + out->kept[k];
+    const size_t total = (size_t)out->first[n];
+    out->start.resize(total); out->end.resize(total); out->ordinal.resize(total);
+    for (size_t k = 0; k < n; k++) {
+        std::copy(st[k].begin(), st[k].end(), out->start.begin() + out->first[k]);
+        std::copy(en[k].begin(), en[k].end(), out->end.begin() + out->first[k]);
+        std::copy(ord[k].begin(), ord[k].end(), out->ordinal.begin() + out->first[k]);
+    }
 }
 
 }  // namespace parsnp
