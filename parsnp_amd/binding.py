@@ -52,11 +52,7 @@ class Lib:
     def gap_limits_long(self):
         """(sequences, bases of a sequence, columns of an alignment) of the device gap aligner's long form: pm_gap_limits_long, the
         limits of pm_gap_align_groups_long (gaps of a cluster distance d of up to 1 000)"""
-        if not hasattr(self.L, "pm_gap_limits_long"):
-            raise PmError("this provider of the ABI has no pm_gap_limits_long")
-        a, b, c = C.c_int(), C.c_int(), C.c_int()
-        self._check(self.L.pm_gap_limits_long(C.byref(a), C.byref(b), C.byref(c)))
-        return a.value, b.value, c.value
+        return self._gap_limits_of("pm_gap_limits_long")
 
     def gap_limits_tall(self):
         """(sequences, bases of a sequence, columns of an alignment) of the device gap aligner's tall form: pm_gap_limits_tall, the

@@ -48,16 +48,10 @@
 #include <vector>
 
 #include "../../../include/parsnp_mum.h"
+#include "gap_plan.h"      // the forms' limits (kMaxSeqs ... kLongTallSeqs), Job, tb_bytes, slot_bytes; the host's plan of a call
 
 namespace {
 
-constexpr int kMaxSeqs = 512;      // sequences per alignment on the device: narrow and wide form
-constexpr int kTallSeqs = 2048;    // ... and in the tall form (columns and bases: those of the wide form)
-constexpr size_t kTallWorkspace = (size_t)8 << 30;      // bytes of slot workspace a tall launch may ask for (a slot of 2 048 sequences needs 20 MB)
-constexpr int kMaxCols = 96;       // narrow form: bases of a sequence and columns of any intermediate alignment (LDS per wavefront ~25 KB: 6 alignments in flight per CU)
-constexpr int kWideSeq = 320;      // wide form: bases of a sequence (every gap the default d = 300 of the reference's driver can produce) ...
-constexpr int kWideCols = 640;     // ... and columns of any intermediate alignment (300-base strings align to about 1.65 times their length)
-constexpr int kTable = 46656;      // 6^6 (fastdistnuc.cpp:82)
 constexpr float kMinusInf = (float)-1e37;
 constexpr float kBigDist = (float)1e29;
 constexpr float kGapOpen = -400.0f;
@@ -73,8 +67,6 @@ __constant__ float c_matrix[4][4] = {      // nucmx.cpp:8-25: BLASTZ scores + 2*
     {-123.0f + 60.0f, -31.0f + 60.0f, -114.0f + 60.0f, 91.0f + 60.0f},
 };
 __constant__ uint8_t c_letter[256];         // alpha.cpp:125-166: 0..3 residues, 4..15 wildcards, 16 gap, 255 none
-
-struct Job { int64_t first_seq; int32_t n; int32_t max_cols; int64_t row_off; };
 
 // per-slot workspace (global memory), sized for the widest job of the launch
 struct Slot {
@@ -130,7 +122,7 @@ __device__ inline uint8_t row_char(uint8_t b) { const uint8_t c = b & kRowCode; 
 // the compiler must take every `return false` and every loop exit of a job for divergent (it cannot see that a butterfly sum or an
 // LDS word is the same in all lanes), structures the job loop as nested exec-mask loops in which "returned" lanes wait for the
 // others, and a build without the stage markers hung in that structure on the device (round 3, reproduced in round 5:
-// scripts/gap_nomark.sh; the markers' branches happened to break it up).  Uniform by construction; said so, it is also cheaper.
+// profiles/r05/gap_hang.md; the markers' branches happened to break it up).  Uniform by construction; said so, it is also cheaper.
 __device__ inline int uni(int x) { return __builtin_amdgcn_readfirstlane(x); }
 __device__ inline unsigned uni(unsigned x) { return (unsigned)__builtin_amdgcn_readfirstlane((int)x); }
 __device__ inline float uni(float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); }
@@ -391,7 +383,7 @@ __device__ bool nw_small(Sh& S, uint8_t* TB, int la, int lb, int* plen, bool pro
 }
 
 // -DPM_GAP_NO_MARKERS: the kernel without its stage markers and stage clocks (what hung once in round 3, on that round's kernel;
-// measurement builds only: `make -C parsnp_amd/csrc nomark`, scripts/gap_nomark.sh)
+// measurement builds only: `make -C parsnp_amd/csrc nomark`)
 #if defined(PM_GAP_NO_MARKERS) || defined(PM_GAP_NO_STAGES)
 constexpr bool kGapStages = false;      // the (job, stage) markers of PM_GAP_DEBUG=1|2
 #else
@@ -402,14 +394,7 @@ constexpr bool kGapClocks = false;      // the stage clocks of PM_GAP_DEBUG=3
 #else
 constexpr bool kGapClocks = true;
 #endif
-// (-DPM_GAP_STRIP_STAGE=s: ONE marker compiled out -- s = 1 ... 7 the stages, 100 the three markers of the merge loop, 900 the job
-// markers of the kernel's loop: which marker's absence the hang of the marker-free build needs, scripts/gap_nomark.sh)
-#if !defined(PM_GAP_STRIP_STAGE)
-#define PM_GAP_STRIP_STAGE (-1)
-#endif
-constexpr bool ga_stage_on(int s) { return kGapStages && !(PM_GAP_STRIP_STAGE == s || (PM_GAP_STRIP_STAGE == 100 && s >= 100 && s < 900)); }
-#define GA_STAGE(stage_) do { if (ga_stage_on(stage_) && P.dbg && lane == 0) P.dbg[blockIdx.x * 2 + 1] = (stage_); } while (0)
-#define GA_STAGE_DYN(stage_) do { if (P.dbg && lane == 0) P.dbg[blockIdx.x * 2 + 1] = (stage_); } while (0)
+#define GA_STAGE(stage_) do { if (kGapStages && P.dbg && lane == 0) P.dbg[blockIdx.x * 2 + 1] = (stage_); } while (0)
 // PM_GAP_DEBUG=3: the shader clock spent since the previous mark goes to stage k_
 // (kept in registers and added to the launch's totals once per job: a shared counter per mark would be what is measured)
 #define GA_CLOCK(k_) do { if (kGapClocks && P.prof) { const unsigned long long t_ = (unsigned long long)clock64(); prof_acc[(k_)] += t_ - prof_t0; prof_t0 = t_; } } while (0)
@@ -418,12 +403,10 @@ constexpr bool ga_stage_on(int s) { return kGapStages && !(PM_GAP_STRIP_STAGE ==
 // the call): lane 0 leaves it, lanes 1-63 go round the job body again and never leave -- the kernel hangs on the first batch of more
 // than one job.  The (job, stage) markers of PM_GAP_DEBUG happened to break that structure up, which is why only a build WITHOUT them
 // hung (round 3; reproduced, bisected to the two job markers of the kernel's loop and read off the ISA in round 5: DESIGN.md 9-6,
-// scripts/gap_nomark.sh).  As a call the job is one node of the loop's control flow; -DPM_GAP_INLINE restores the old shape for the
-// regression check.  tests/test_gpu_gapalign.py::test_marker_free_build runs the marker-free build.
+// profiles/r05/gap_hang.md).  As a call the job is one node of the loop's control flow.
+// tests/test_gpu_gapalign.py::test_marker_free_build runs the marker-free build.
 template <class Sh>
-#if !defined(PM_GAP_INLINE)
 __attribute__((noinline))
-#endif
 __device__ bool align_job(Sh& S, uint8_t* R, uint8_t* TB, const Slot& W, const Params& P, const Job& job, int* out_cols) {
     const int lane = (int)__lane_id();
     const int n = job.n, cap = P.cap;
@@ -672,14 +655,14 @@ __device__ bool align_job(Sh& S, uint8_t* R, uint8_t* TB, const Slot& W, const P
         const float total_a = a < un ? 0.0f + S.wrow[loa] : S.total_i[a - un];
         const float total_b = b < un ? 0.0f + S.wrow[lob] : S.total_i[b - un];
         if (la <= 0 || lb <= 0 || la > Sh::kCols || lb > Sh::kCols) return false;
-        if (ga_stage_on(100)) GA_STAGE_DYN(100 + (int)(v - un) * 10);
+        GA_STAGE(100 + (int)(v - un) * 10);
         GA_CLOCK(8);
         if (any_wild) { build_profile<true>(S, R, cap, loa, nsa, la, total_a, true); build_profile<true>(S, R, cap, lob, nsb, lb, total_b, false); }
         else { build_profile<false>(S, R, cap, loa, nsa, la, total_a, true); build_profile<false>(S, R, cap, lob, nsb, lb, total_b, false); }
         int plen = 0;
-        if (ga_stage_on(100)) GA_STAGE_DYN(101 + (int)(v - un) * 10); GA_CLOCK(13);
+        GA_STAGE(101 + (int)(v - un) * 10); GA_CLOCK(13);
         if (!nw_small(S, TB, la, lb, &plen, kGapClocks && P.prof != nullptr, prof_acc[9], prof_t0)) return false;
-        if (ga_stage_on(100)) GA_STAGE_DYN(102 + (int)(v - un) * 10); GA_CLOCK(10);
+        GA_STAGE(102 + (int)(v - un) * 10); GA_CLOCK(10);
         if (plen > cap || plen > Sh::kCols) return false;
         // aligngivenpath.cpp:124-255: a column of A, of B, or of both
         // (a column's place in A / in B = the number of A / B columns before it: counted with ballots)
@@ -806,9 +789,7 @@ __device__ bool align_job(Sh& S, uint8_t* R, uint8_t* TB, const Slot& W, const P
     return true;
 }
 
-// the trace-back bytes of one pairwise DP of up to cap x cap columns (nw_small)
-__host__ __device__ inline size_t tb_bytes(int cap) { return ((size_t)cap + 1) * ((size_t)cap + 1); }
-// seq: the form's limit on the bases of a sequence; rows / tb: the alignment rows and the trace-back bytes are in the workspace
+// (tb_bytes, slot_bytes: gap_plan.h)  seq: the form's limit on the bases of a sequence; rows / tb: the alignment rows and the trace-back bytes are in the workspace
 __device__ Slot carve(uint8_t* base, int nmax, int cap, int seq, bool rows, bool tb) {
     Slot W;
     size_t off = 0;
@@ -835,14 +816,6 @@ __device__ Slot carve(uint8_t* base, int nmax, int cap, int seq, bool rows, bool
     W.tb = tb ? take(tb_bytes(cap)) : nullptr;
     return W;
 }
-size_t slot_bytes(int nmax, int cap, int seq, bool rows, bool tb) {
-    const size_t n = (size_t)nmax;
-    auto r = [](size_t b) { return (b + 15) & ~(size_t)15; };
-    return r(4 * (n * (n - 1) / 2 + 1)) + r(2 * n * n) + r(2 * n * (size_t)seq) + r(n * (size_t)seq) + r(4 * n) + r(8 * n) + 4 * r(4 * n) + 3 * r(8 * n) + r(16 * n) +
-           r(4 * n) + r(8 * n) + r(16 * n) + r(4 * n) + 2 * r(8 * n) + r(4 * n) + r(8 * n) + r(kTable) + (rows ? r(n * (size_t)cap) : 0) +
-           (tb ? r(tb_bytes(cap)) : 0) + 256;
-}
-
 // Sh = Shared: the narrow form, its fixed block static and rows + trace-back bytes behind it as dynamic LDS.
 // Sh = SharedWide: the fixed block itself is dynamic LDS (54 KB), then the rows and the trace-back bytes -- each only when the launch
 // found room for it (Params::rows_ws / tb_ws: it is in the slot's workspace instead; align_job reads both through flat pointers)
@@ -872,12 +845,12 @@ __global__ __launch_bounds__(64) void gap_align_kernel(Params P) {
         GA_SYNC();
         if (j >= P.njobs) break;
         const Job job = P.jobs[j];
-        if (ga_stage_on(900) && P.dbg && threadIdx.x == 0) { P.dbg[blockIdx.x * 2] = (int32_t)j; P.dbg[blockIdx.x * 2 + 1] = 0; }
+        if (kGapStages && P.dbg && threadIdx.x == 0) { P.dbg[blockIdx.x * 2] = (int32_t)j; P.dbg[blockIdx.x * 2 + 1] = 0; }
         int cols = -1;
         if (!align_job(S, R, TB, W, P, job, &cols)) cols = -1;
         GA_SYNC();
         if (threadIdx.x == 0) P.out_cols[j] = cols;
-        if (ga_stage_on(900) && P.dbg && threadIdx.x == 0) P.dbg[blockIdx.x * 2 + 1] = -1;
+        if (kGapStages && P.dbg && threadIdx.x == 0) P.dbg[blockIdx.x * 2 + 1] = -1;
     }
 }
 
@@ -896,20 +869,15 @@ __global__ __launch_bounds__(64) void gap_align_kernel(Params P) {
 // stage that stays on wavefront 0 (the ordered compactions, the guide tree's merges, the weights, the trace-back, the column
 // maps) is an `if (wave == 0)` without a barrier inside -- its lanes order their own memory traffic with GA_WAVE_SYNC -- and
 // the others wait at the barrier behind it.  A job is given up through S.fail, read by everybody after a barrier.
-constexpr int kLongSeqs = 512, kLongSeq = 1024, kLongCols = 2048;
-constexpr int kLongThreads = 256;
 constexpr int kLongChunk = 64;      // DP steps between two barriers of the sweep
 constexpr int kLongLag = 2;         // chunks a wavefront runs behind the one above it (see nw_long)
 constexpr int kLongRing = 256;      // columns of a hand-over ring (power of two)
-constexpr size_t kLongWorkspace = (size_t)8 << 30;      // bytes of slot workspace a long launch may ask for (a slot of 512 x 2 048 needs 8 MB)
-constexpr size_t kLongAccBytes = (size_t)6 * 4 * kLongCols;
 
 // the lanes of ONE wavefront: their outstanding loads / stores have completed before any of them goes on
 #define GA_WAVE_SYNC() do { __builtin_amdgcn_s_waitcnt(0); __threadfence_block(); __builtin_amdgcn_wave_barrier(); } while (0)
 
 // kSeqs_: the sequences of a job.  kTotalWs: the per-node weight totals lie in the slot's workspace (Slot::total), not in LDS -- the
 // long-tall form (kLongTallSeqs), whose per-sequence arrays would otherwise push the block past the LDS of a CU
-constexpr int kLongTallSeqs = 2048;
 template <int kSeqs_, bool kTotalWs_>
 struct __align__(16) SharedLongT {
     static constexpr int kCols = kLongCols, kSeq = kLongSeq, kSeqs = kSeqs_;
@@ -1159,9 +1127,7 @@ __device__ bool nw_long(Sh& S, uint8_t* TB, int la, int lb, int* plen, bool prof
 
 // align_job for a workgroup of kLongThreads threads (the comment above it tells why this is a call, not inlined)
 template <class Sh>
-#if !defined(PM_GAP_INLINE)
 __attribute__((noinline))
-#endif
 __device__ bool align_job_long(Sh& S, uint8_t* R, uint8_t* TB, float* ACC, const Slot& W, const Params& P, const Job& job, int* out_cols) {
     constexpr int T = kLongThreads;
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = uni(tid >> 6);
@@ -1433,14 +1399,14 @@ __device__ bool align_job_long(Sh& S, uint8_t* R, uint8_t* TB, float* ACC, const
         const float total_a = a < un ? 0.0f + S.wrow[loa] : S.total(W, a - un);
         const float total_b = b < un ? 0.0f + S.wrow[lob] : S.total(W, b - un);
         if (la <= 0 || lb <= 0 || la > Sh::kCols || lb > Sh::kCols) return false;
-        if (ga_stage_on(100)) GA_STAGE_DYN(100 + (int)(v - un) * 10);
+        GA_STAGE(100 + (int)(v - un) * 10);
         GA_CLOCK(8);
         if (any_wild) { build_profile_long<true>(S, R, ACC, cap, loa, nsa, la, total_a, true); build_profile_long<true>(S, R, ACC, cap, lob, nsb, lb, total_b, false); }
         else { build_profile_long<false>(S, R, ACC, cap, loa, nsa, la, total_a, true); build_profile_long<false>(S, R, ACC, cap, lob, nsb, lb, total_b, false); }
         int plen = 0;
-        if (ga_stage_on(100)) GA_STAGE_DYN(101 + (int)(v - un) * 10); GA_CLOCK(13);
+        GA_STAGE(101 + (int)(v - un) * 10); GA_CLOCK(13);
         if (!nw_long(S, TB, la, lb, &plen, kGapClocks && P.prof != nullptr, prof_acc[9], prof_t0)) return false;
-        if (ga_stage_on(100)) GA_STAGE_DYN(102 + (int)(v - un) * 10); GA_CLOCK(10);
+        GA_STAGE(102 + (int)(v - un) * 10); GA_CLOCK(10);
         if (plen > cap || plen > Sh::kCols) return false;
         // aligngivenpath.cpp:124-255: a column of A, of B, or of both (counted with the ballots of wavefront 0)
         if (wave == 0) {
@@ -1544,12 +1510,12 @@ __global__ __launch_bounds__(kLongThreads) void gap_align_long_kernel(Params P) 
         GA_SYNC();
         if (j >= P.njobs) break;
         const Job job = P.jobs[j];
-        if (ga_stage_on(900) && P.dbg && lane == 0) { P.dbg[blockIdx.x * 2] = (int32_t)j; P.dbg[blockIdx.x * 2 + 1] = 0; }
+        if (kGapStages && P.dbg && lane == 0) { P.dbg[blockIdx.x * 2] = (int32_t)j; P.dbg[blockIdx.x * 2 + 1] = 0; }
         int cols = -1;
         if (!align_job_long(S, W.rows, W.tb, ACC, W, P, job, &cols)) cols = -1;
         GA_SYNC();
         if (threadIdx.x == 0) P.out_cols[j] = cols;
-        if (ga_stage_on(900) && P.dbg && lane == 0) P.dbg[blockIdx.x * 2 + 1] = -1;
+        if (kGapStages && P.dbg && lane == 0) P.dbg[blockIdx.x * 2 + 1] = -1;
     }
 }
 
@@ -1610,25 +1576,57 @@ extern "C" int64_t pm_gap_debug_peek(int32_t* out, int64_t cap) {
 }
 
 namespace {
-// One call of any of the six entry points.  level = 0: pm_gap_align_batch / pm_gap_align_groups, the narrow form alone, with the
-// limits and the launch they have always had.  level = 1: pm_gap_align_groups_wide -- a job with a sequence of more than kMaxCols
-// bases goes to the wide form, and a job the narrow form declined whose rows may be wider than kMaxCols is run again in the wide
-// form before its group is reported.  level = 2: pm_gap_align_groups_tall -- the same, and a job of more than kMaxSeqs sequences
-// goes to the tall form (which has the wide form's columns: nothing it declines would fare better in a second run).  level = 3:
-// pm_gap_align_groups_long -- what level 1 does, and a job with a sequence of more than kWideSeq bases goes to the long form.
-// level = 4: pm_gap_align_groups_long_tall -- what levels 2 and 3 do, and a job of more than kMaxSeqs sequences with a sequence of
-// more than kWideSeq bases goes to the long-tall form: the whole rectangle kLongTallSeqs x kLongSeq.
-struct FormStats { int64_t jobs_narrow, jobs_wide, jobs_tall, jobs_long, jobs_long_tall, declined; double ms_narrow, ms_wide, ms_tall, ms_long, ms_long_tall; };
-constexpr int kForms = 5;         // ranges of a group in the sorted job list: narrow, wide, tall, long, long-tall
-constexpr int kCounters = 6;      // queue counters of a group, one per launch: narrow, wide, wide again, tall, long, long-tall
-int align_groups(int level, int device, int64_t n_jobs, const int32_t* n_seqs, const int64_t* seq_off, const uint8_t* chars,
+// c_letter of the current device, uploaded on its first call
+hipError_t upload_letters() {
+    hipError_t table_err = hipSuccess;
+    int cur_dev = 0;
+    (void)hipGetDevice(&cur_dev);
+    std::lock_guard<std::mutex> lk(g_tables_mu);
+    if (cur_dev < 0 || cur_dev >= 64 || !g_tables_ready[cur_dev]) {
+        uint8_t letter[256];
+        memset(letter, 255, sizeof letter);
+        const char* res = "ACGT";
+        for (int i = 0; i < 4; i++) { letter[(uint8_t)res[i]] = (uint8_t)i; letter[(uint8_t)(res[i] + 32)] = (uint8_t)i; }
+        letter[(uint8_t)'U'] = letter[(uint8_t)'u'] = 3;
+        const char* wild = "MRWSYKVHDBXN";
+        for (int i = 0; i < 12; i++) { letter[(uint8_t)wild[i]] = (uint8_t)(4 + i); letter[(uint8_t)(wild[i] + 32)] = (uint8_t)(4 + i); }
+        letter[(uint8_t)'-'] = letter[(uint8_t)'.'] = 16;
+        table_err = hipMemcpyToSymbol(HIP_SYMBOL(c_letter), letter, 256);
+        if (table_err == hipSuccess && cur_dev >= 0 && cur_dev < 64) g_tables_ready[cur_dev] = true;
+    }
+    return table_err;
+}
+// the kernel of a form.  (The kernels are named in the order in which the launches used to
+// name them: that is the order of the functions in the code object, which stays byte for byte what it was.)
+using Kernel = void (*)(Params);
+Kernel kernel_of(Form form) {
+    switch (form) {
+        case kNarrow: return gap_align_kernel<Shared>;
+        case kTall: return gap_align_kernel<SharedTall>;
+        case kWide: return gap_align_kernel<SharedWide>;
+        case kLongTall: return gap_align_long_kernel<SharedLongTall>;
+        default: return gap_align_long_kernel<SharedLong>;
+    }
+}
+// the fixed blocks have the sizes that the plan of a launch counts with (the table of gap_plan.h, which cannot see the structs)
+static_assert(sizeof(Shared) == kFormTable[kNarrow].fixed && sizeof(SharedWide) == kFormTable[kWide].fixed && sizeof(SharedTall) == kFormTable[kTall].fixed &&
+              sizeof(SharedLong) == kFormTable[kLong].fixed && sizeof(SharedLongTall) == kFormTable[kLongTall].fixed, "gap_plan.h: FormRow::fixed");
+static_assert(sizeof(Shared) % 16 == 0, "the narrow form's rows start right behind its fixed block");
+struct FormStats { int64_t jobs[kForms]; double ms[kForms]; int64_t declined; };
+
+// One call of any of the six entry points; `rect` is what the entry point accepts (gap_plan.h).  A job goes to the smallest form
+// that holds it (route), and -- unless rect.narrow_only -- a job the narrow form declined whose rows may be wider than kMaxCols is
+// run again in the wide form before its group is reported.  (The tall and the long forms have the columns of the forms below them:
+// nothing they decline would fare better in a second run.)
+// Top to bottom: plan, upload, then per group launch its forms, run the declined narrow jobs again wide, copy back, report.
+int align_groups(const Rect& rect, int device, int64_t n_jobs, const int32_t* n_seqs, const int64_t* seq_off, const uint8_t* chars,
                  const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols,
                  int n_groups, const int64_t* group_end, void (*done)(void* ctx, int group), void* ctx, FormStats* stats) {
-    const bool wide = level >= 1;
-    if (stats) *stats = FormStats{0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    if (n_jobs < 0 || (n_jobs > 0 && (!n_seqs || !seq_off || !chars || !max_cols || !row_off || !out_rows || !cols))) return fail(PM_EINVAL, "bad argument");
-    if (n_groups < 1 || !group_end || group_end[n_groups - 1] != n_jobs) return fail(PM_EINVAL, "bad job groups");
-    for (int g = 0; g < n_groups; g++) if (group_end[g] < (g ? group_end[g - 1] : 0)) return fail(PM_EINVAL, "bad job groups");
+    if (stats) *stats = FormStats{};
+    Plan plan = plan_jobs(rect, n_jobs, n_seqs, seq_off, chars, max_cols, row_off, out_rows, out_bytes, cols, n_groups, group_end);
+    if (plan.error) return fail(PM_EINVAL, plan.error);
+    const std::vector<Job>& jobs = plan.jobs;
+    const std::vector<size_t>& first = plan.first;
     auto all_done = [&](int from) { if (done) for (int g = from; g < n_groups; g++) done(ctx, g); };
     if (n_jobs == 0) { all_done(0); return PM_OK; }
     int count = 0;
@@ -1641,67 +1639,10 @@ int align_groups(int level, int device, int64_t n_jobs, const int32_t* n_seqs, c
     std::vector<hipEvent_t> events;
     auto release = [&]() { for (void* p : owned) (void)hipFree(p); owned.clear(); for (hipEvent_t e : events) (void)hipEventDestroy(e); events.clear();
                            if (stream) { (void)hipStreamDestroy(stream); stream = nullptr; } };
-    {
-        hipError_t table_err = hipSuccess;
-        int cur_dev = 0;
-        (void)hipGetDevice(&cur_dev);
-        std::lock_guard<std::mutex> lk(g_tables_mu);
-        if (cur_dev < 0 || cur_dev >= 64 || !g_tables_ready[cur_dev]) {
-            uint8_t letter[256];
-            memset(letter, 255, sizeof letter);
-            const char* res = "ACGT";
-            for (int i = 0; i < 4; i++) { letter[(uint8_t)res[i]] = (uint8_t)i; letter[(uint8_t)(res[i] + 32)] = (uint8_t)i; }
-            letter[(uint8_t)'U'] = letter[(uint8_t)'u'] = 3;
-            const char* wild = "MRWSYKVHDBXN";
-            for (int i = 0; i < 12; i++) { letter[(uint8_t)wild[i]] = (uint8_t)(4 + i); letter[(uint8_t)(wild[i] + 32)] = (uint8_t)(4 + i); }
-            letter[(uint8_t)'-'] = letter[(uint8_t)'.'] = 16;
-            table_err = hipMemcpyToSymbol(HIP_SYMBOL(c_letter), letter, 256);
-            if (table_err == hipSuccess && cur_dev >= 0 && cur_dev < 64) g_tables_ready[cur_dev] = true;
-        }
-        GA_CHECK(table_err);
-    }
-    // jobs the device takes, per group the narrow ones, then the wide ones, the tall ones, the long ones, the long-tall ones, each longest first
-    // (the cost of one alignment grows with the square of its width)
-    std::vector<Job> jobs; std::vector<int64_t> which; std::vector<int> group_of_job, form_of_job;
-    int64_t seq = 0, total_chars = 0;
-    int nmax = 2, cap = 1;             // of the narrow form: the widest job of the call
-    std::vector<int> widest((size_t)n_jobs, 0);
-    const int seq_limit = level >= 3 ? kLongSeq : (wide ? kWideSeq : kMaxCols), seqs_limit = level == 2 ? kTallSeqs : (level == 4 ? kLongTallSeqs : kMaxSeqs);
-    int grp = 0;
-    for (int64_t j = 0; j < n_jobs; j++) {
-        while (grp + 1 < n_groups && j >= group_end[grp]) grp++;
-        cols[j] = -1;
-        const int n = n_seqs[j];
-        int w = 0; bool ok = n >= 2 && n <= seqs_limit && max_cols[j] >= 1;
-        for (int i = 0; i < n && ok; i++) { const int64_t L = seq_off[seq + i + 1] - seq_off[seq + i]; if (L <= 0 || L > seq_limit) ok = false; else w = std::max<int>(w, (int)L); }
-        if (ok && row_off[j] + (int64_t)n * max_cols[j] > out_bytes) ok = false;
-        if (ok) {
-            const int form = n > kMaxSeqs ? 2 : (w > kWideSeq ? 3 : (w > kMaxCols ? 1 : 0));
-            const int routed = form == 2 && w > kWideSeq ? 4 : form;      // more than kMaxSeqs sequences AND a string above kWideSeq (level 4 alone lets one through): the long-tall form
-            jobs.push_back(Job{seq, n, max_cols[j], row_off[j]}); which.push_back(j); group_of_job.push_back(grp); form_of_job.push_back(routed); widest[(size_t)j] = w;
-            if (!routed) { nmax = std::max(nmax, n); cap = std::max(cap, std::min<int>(max_cols[j], kMaxCols)); }
-        }
-        seq += n;
-    }
-    total_chars = seq_off[seq];
+    GA_CHECK(upload_letters());
+    const int64_t seq = plan.seqs, total_chars = seq_off[seq];
     auto count_declined = [&]() { if (stats) { stats->declined = 0; for (int64_t j = 0; j < n_jobs; j++) stats->declined += cols[j] < 0; } };
     if (jobs.empty()) { count_declined(); all_done(0); return PM_OK; }
-    // in the sorted job list: group g = [first[5g], first[5g+5]), its narrow jobs first, its wide jobs from first[5g+1], its tall
-    // jobs from first[5g+2], its long jobs from first[5g+3], its long-tall jobs from first[5g+4]
-    std::vector<size_t> first((size_t)n_groups * kForms + 1, 0);
-    {
-        std::vector<size_t> order(jobs.size());
-        for (size_t i = 0; i < order.size(); i++) order[i] = i;
-        std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) {
-            if (group_of_job[a] != group_of_job[b]) return group_of_job[a] < group_of_job[b];
-            if (form_of_job[a] != form_of_job[b]) return form_of_job[a] < form_of_job[b];
-            return widest[(size_t)which[a]] > widest[(size_t)which[b]];
-        });
-        std::vector<Job> j2; std::vector<int64_t> w2;
-        for (size_t i : order) { j2.push_back(jobs[i]); w2.push_back(which[i]); first[(size_t)group_of_job[i] * kForms + (size_t)form_of_job[i] + 1]++; }
-        for (size_t k = 0; k < (size_t)n_groups * kForms; k++) first[k + 1] += first[k];
-        jobs.swap(j2); which.swap(w2);
-    }
     const bool timers = getenv("PARSNP_DEBUG_TIMERS") != nullptr;
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double tl = now();
@@ -1711,22 +1652,17 @@ int align_groups(int level, int device, int64_t n_jobs, const int32_t* n_seqs, c
     GA_CHECK(hipGetDeviceProperties(&prop, device));
     GA_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     auto dalloc = [&](size_t bytes, void** p) { hipError_t e = hipMalloc(p, bytes ? bytes : 1); if (e == hipSuccess) owned.push_back(*p); return e; };
-    const bool any_narrow = [&] { for (int g = 0; g < n_groups; g++) if (first[(size_t)g * kForms + 1] > first[(size_t)g * kForms]) return true; return false; }();
-    // ---- the narrow form.  LDS of a workgroup: the fixed block plus the alignment rows of the widest job and the trace-back bytes;
-    // as many workgroups per CU as fit in 160 KB
-    constexpr size_t kLdsLimit = 160 * 1024 - 1024;
-    const size_t rows_lds = ((((size_t)nmax * (size_t)cap) + 15) & ~(size_t)15) + ((((size_t)cap + 1) * ((size_t)cap + 1) + 15) & ~(size_t)15);
-    const size_t lds = sizeof(Shared) + rows_lds;
-    int per_cu = 0; int64_t slots = 0; size_t stride = 0;
-    uint8_t* d_ws = nullptr;
-    if (any_narrow) {
-        if (lds > kLdsLimit) { release(); return fail(PM_ELIMIT, "gap alignment rows do not fit the LDS"); }
-        if (lds > 64 * 1024) GA_CHECK(hipFuncSetAttribute((const void*)gap_align_kernel<Shared>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rows_lds));
-        per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / (lds + 256)));
-        size_t most = 0;      // narrow jobs of one group (without a wide job in the call: of the call, as the launch has always been sized)
-        for (int g = 0; g < n_groups; g++) most = std::max(most, first[(size_t)g * kForms + 1] - first[(size_t)g * kForms]);
-        slots = std::min<int64_t>(wide ? (int64_t)most : (int64_t)jobs.size(), (int64_t)prop.multiProcessorCount * per_cu);
-        stride = slot_bytes(nmax, cap, kMaxCols, false, false);
+    // ---- the narrow form is sized once, by the widest narrow job of the call and the narrow jobs of its largest group (narrow_only:
+    // by all jobs of the call, as that launch has always been sized), and its workspace is allocated up front; the other forms are
+    // sized launch by launch and share one workspace that grows (size_launch, gap_plan.h)
+    struct Workspace { uint8_t* p; size_t bytes; };
+    Workspace narrow_ws{nullptr, 0}, shared_ws{nullptr, 0};
+    Geometry narrow{};
+    size_t most = 0;
+    for (int g = 0; g < n_groups; g++) most = std::max(most, first[(size_t)g * kForms + 1] - first[(size_t)g * kForms]);
+    if (most) {
+        narrow = size_launch(kNarrow, plan.nmax, plan.cap, rect.narrow_only ? jobs.size() : most, prop.multiProcessorCount, 0);
+        if (!narrow.fits) { release(); return fail(PM_ELIMIT, "gap alignment rows do not fit the LDS"); }
     }
     Job* d_jobs; int64_t* d_off; uint8_t* d_chars; uint8_t* d_out; int32_t* d_cols; unsigned long long* d_next;
     GA_CHECK(dalloc(sizeof(Job) * jobs.size(), (void**)&d_jobs));
@@ -1734,15 +1670,15 @@ int align_groups(int level, int device, int64_t n_jobs, const int32_t* n_seqs, c
     GA_CHECK(dalloc((size_t)total_chars, (void**)&d_chars));
     GA_CHECK(dalloc((size_t)out_bytes, (void**)&d_out));
     GA_CHECK(dalloc(4 * jobs.size(), (void**)&d_cols));
-    GA_CHECK(dalloc(8 * kCounters * (size_t)n_groups, (void**)&d_next));      // a queue counter per launch: narrow, wide, wide again, tall, long, long-tall
-    if (any_narrow) GA_CHECK(dalloc(stride * (size_t)slots, (void**)&d_ws));
+    GA_CHECK(dalloc(8 * kCounters * (size_t)n_groups, (void**)&d_next));      // a queue counter per launch of a group
+    if (most) { narrow_ws.bytes = narrow.stride * (size_t)narrow.slots; GA_CHECK(dalloc(narrow_ws.bytes, (void**)&narrow_ws.p)); }
     GA_CHECK(hipMemcpyAsync(d_jobs, jobs.data(), sizeof(Job) * jobs.size(), hipMemcpyHostToDevice, stream));
     GA_CHECK(hipMemcpyAsync(d_off, seq_off, 8 * (size_t)(seq + 1), hipMemcpyHostToDevice, stream));
     GA_CHECK(hipMemcpyAsync(d_chars, chars, (size_t)total_chars, hipMemcpyHostToDevice, stream));
     GA_CHECK(hipMemsetAsync(d_next, 0, 8 * kCounters * (size_t)n_groups, stream));
     if (timers) { GA_CHECK(hipStreamSynchronize(stream)); lap("alloc + h2d"); }
     int32_t* dbg = nullptr;
-    const int64_t dbg_slots = std::max<int64_t>(slots, wide ? (int64_t)prop.multiProcessorCount * 8 : 0);
+    const int64_t dbg_slots = std::max<int64_t>(narrow.slots, rect.narrow_only ? 0 : (int64_t)prop.multiProcessorCount * 8);
     if (getenv("PM_GAP_DEBUG") && atoi(getenv("PM_GAP_DEBUG")) == 2) {
         if (g_dbg_dev) (void)hipFree(g_dbg_dev);
         g_dbg_dev = nullptr;
@@ -1756,119 +1692,74 @@ int align_groups(int level, int device, int64_t n_jobs, const int32_t* n_seqs, c
         GA_CHECK(dalloc(8 * kProfStages, (void**)&d_prof));
         GA_CHECK(hipMemsetAsync(d_prof, 0, 8 * kProfStages, stream));
     }
-    if (timers && any_narrow) fprintf(stderr, "[gap batch] %zu jobs in %d group(s), widest %d sequences x %d columns: %zu B of LDS per wavefront, %d per CU, %lld slots\n", jobs.size(), n_groups, nmax, cap, lds, per_cu, (long long)slots);
-    // ---- the wide form: sized per launch by the jobs it is given.  Where things live: the fixed block (SharedWide) always in LDS;
-    // the rows (n x cap bytes) in LDS when they fit beside it, and the trace-back bytes (tb_bytes) too when both fit; what does not
-    // fit lies in the slot's workspace, which one wavefront re-reads out of L2.  No job is declined for its size in LDS.
-    // PM_GAP_WIDE_PLACE (measurements): 1 the trace-back bytes, 2 the rows, 3 both in the workspace whatever fits.
-    uint8_t* d_wide_ws = nullptr; size_t wide_ws_bytes = 0;
+    if (timers && most) fprintf(stderr, "[gap batch] %zu jobs in %d group(s), widest %d sequences x %d columns: %zu B of LDS per wavefront, %d per CU, %lld slots\n", jobs.size(), n_groups, narrow.wn, narrow.wc, narrow.lds, narrow.per_cu, (long long)narrow.slots);
     Job* d_again = nullptr; int32_t* d_again_cols = nullptr;      // the jobs of a second wide launch, and their column counts
     const int place = getenv("PM_GAP_WIDE_PLACE") ? atoi(getenv("PM_GAP_WIDE_PLACE")) : 0;
-    struct Timed { hipEvent_t a, b; int form; };
+    struct Timed { hipEvent_t a, b; Form form; };
     std::vector<Timed> timed;
     auto mark = [&](hipEvent_t* e) { hipError_t r = hipEventCreate(e); if (r == hipSuccess) { events.push_back(*e); r = hipEventRecord(*e, stream); } return r; };
-    // (form 2, the tall form: the same launch with SharedTall as its fixed block, and no more slots than kTallWorkspace allows)
-    auto launch_wide = [&](int form, const Job* host_jobs, size_t nj, const Job* dev_jobs, int32_t* dev_cols, unsigned long long* counter) -> hipError_t {
-        void (*const kernel)(Params) = form == 2 ? gap_align_kernel<SharedTall> : gap_align_kernel<SharedWide>;
-        int wn = 2, wc = 1;
-        for (size_t i = 0; i < nj; i++) { wn = std::max(wn, host_jobs[i].n); wc = std::max(wc, std::min<int>(host_jobs[i].max_cols, kWideCols)); }
-        auto r16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-        const size_t fixed = r16(form == 2 ? sizeof(SharedTall) : sizeof(SharedWide)), rows_b = r16((size_t)wn * (size_t)wc), tb_b = r16(tb_bytes(wc));
-        bool rows_ws = (place & 2) != 0, tb_ws = (place & 1) != 0;
-        if (!rows_ws && fixed + rows_b > kLdsLimit) rows_ws = true;
-        if (!tb_ws && fixed + (rows_ws ? 0 : rows_b) + tb_b > kLdsLimit) tb_ws = true;
-        const size_t dyn = fixed + (rows_ws ? 0 : rows_b) + (tb_ws ? 0 : tb_b);
-        hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-        if (e != hipSuccess) return e;
-        const int wper_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / (dyn + 256)));
-        const size_t wstride = slot_bytes(wn, wc, kWideSeq, rows_ws, tb_ws);
-        int64_t wslots = std::min<int64_t>((int64_t)nj, (int64_t)prop.multiProcessorCount * wper_cu);
-        if (form == 2) wslots = std::min<int64_t>(wslots, std::max<int64_t>(1, (int64_t)(kTallWorkspace / wstride)));
-        if (wstride * (size_t)wslots > wide_ws_bytes) {
+    // one launch: nj jobs of one form in geometry G, on min(nj, G.slots) slots of workspace ws
+    auto launch = [&](Form form, const Geometry& G, Workspace& ws, size_t nj, const Job* dev_jobs, int32_t* dev_cols, unsigned long long* counter) -> hipError_t {
+        const FormRow& row = kFormTable[form];
+        const Kernel kernel = kernel_of(form);
+        hipError_t e = hipSuccess;
+        // (the narrow form's fixed block is static: what it asks for reaches the 64 KB a kernel has unasked only with wide rows)
+        if ((form != kNarrow || G.lds > 64 * 1024) && (e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G.dyn)) != hipSuccess) return e;
+        if (G.stride * (size_t)G.slots > ws.bytes) {
             e = hipStreamSynchronize(stream);      // (an earlier launch may still use the smaller one)
             if (e != hipSuccess) return e;
-            if (d_wide_ws) { (void)hipFree(d_wide_ws); owned.erase(std::find(owned.begin(), owned.end(), (void*)d_wide_ws)); d_wide_ws = nullptr; wide_ws_bytes = 0; }
-            e = dalloc(wstride * (size_t)wslots, (void**)&d_wide_ws);
+            if (ws.p) { (void)hipFree(ws.p); owned.erase(std::find(owned.begin(), owned.end(), (void*)ws.p)); ws = Workspace{nullptr, 0}; }
+            e = dalloc(G.stride * (size_t)G.slots, (void**)&ws.p);
             if (e != hipSuccess) return e;
-            wide_ws_bytes = wstride * (size_t)wslots;
+            ws.bytes = G.stride * (size_t)G.slots;
         }
-        if (timers) fprintf(stderr, "[gap batch] %s form: %zu jobs, widest %d sequences x %d columns: %zu B of LDS per wavefront (rows in %s, trace-back in %s), %d per CU, %lld slots, %.1f MB of workspace\n",
-                            form == 2 ? "tall" : "wide", nj, wn, wc, dyn, rows_ws ? "the workspace" : "LDS", tb_ws ? "the workspace" : "LDS", wper_cu, (long long)wslots,
-                            (double)(wstride * (size_t)wslots) / 1048576.0);
-        Params P{dev_jobs, (int64_t)nj, d_off, d_chars, d_out, dev_cols, counter, d_wide_ws, (int64_t)wstride, wn, wc, rows_ws ? 1 : 0, tb_ws ? 1 : 0, dbg, d_prof};
+        if (timers && form != kNarrow) {
+            char where[160];
+            if (row.threads > 64) snprintf(where, sizeof where, "workgroup of %d threads (rows, trace-back and profile sums in the workspace), 1", row.threads);
+            else snprintf(where, sizeof where, "wavefront (rows in %s, trace-back in %s), %d", G.rows_ws ? "the workspace" : "LDS", G.tb_ws ? "the workspace" : "LDS", G.per_cu);
+            fprintf(stderr, "[gap batch] %s form: %zu jobs, widest %d sequences x %d columns: %zu B of LDS per %s per CU, %lld slots, %.1f MB of workspace\n",
+                    row.name, nj, G.wn, G.wc, G.dyn, where, (long long)G.slots, (double)(G.stride * (size_t)G.slots) / 1048576.0);
+        }
+        Params P{dev_jobs, (int64_t)nj, d_off, d_chars, d_out, dev_cols, counter, ws.p, (int64_t)G.stride, G.wn, G.wc, G.rows_ws ? 1 : 0, G.tb_ws ? 1 : 0, dbg, d_prof};
         Timed t{nullptr, nullptr, form};
         if (stats && (e = mark(&t.a)) != hipSuccess) return e;
-        hipLaunchKernelGGL(kernel, dim3((unsigned)wslots), dim3(64), dyn, stream, P);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)std::min<int64_t>((int64_t)nj, G.slots)), dim3((unsigned)row.threads), G.dyn, stream, P);
         if ((e = hipGetLastError()) != hipSuccess) return e;
         if (stats) { if ((e = mark(&t.b)) != hipSuccess) return e; timed.push_back(t); }
         return hipSuccess;
     };
-    // ---- the long form: a workgroup of four wavefronts per slot, one per CU (its fixed block takes most of the LDS); rows, trace-back
-    // bytes and profile sums in the slot's workspace, which also bounds the slots (kLongWorkspace).  Shares the wide launches' workspace.
-    // (tall: the long-tall form -- the same launch with SharedLongTall as its fixed block; a slot of 2 048 x 2 048 needs 31 MB)
-    auto launch_long = [&](bool tall, const Job* host_jobs, size_t nj, const Job* dev_jobs, int32_t* dev_cols, unsigned long long* counter) -> hipError_t {
-        void (*const kernel)(Params) = tall ? gap_align_long_kernel<SharedLongTall> : gap_align_long_kernel<SharedLong>;
-        int wn = 2, wc = 1;
-        for (size_t i = 0; i < nj; i++) { wn = std::max(wn, host_jobs[i].n); wc = std::max(wc, std::min<int>(host_jobs[i].max_cols, kLongCols)); }
-        const size_t dyn = ((tall ? sizeof(SharedLongTall) : sizeof(SharedLong)) + 15) & ~(size_t)15;
-        hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-        if (e != hipSuccess) return e;
-        const size_t wstride = slot_bytes(wn, wc, kLongSeq, true, true) + kLongAccBytes;
-        const int64_t wslots = std::min<int64_t>(std::min<int64_t>((int64_t)nj, (int64_t)prop.multiProcessorCount), std::max<int64_t>(1, (int64_t)(kLongWorkspace / wstride)));
-        if (wstride * (size_t)wslots > wide_ws_bytes) {
-            e = hipStreamSynchronize(stream);      // (an earlier launch may still use the smaller one)
-            if (e != hipSuccess) return e;
-            if (d_wide_ws) { (void)hipFree(d_wide_ws); owned.erase(std::find(owned.begin(), owned.end(), (void*)d_wide_ws)); d_wide_ws = nullptr; wide_ws_bytes = 0; }
-            e = dalloc(wstride * (size_t)wslots, (void**)&d_wide_ws);
-            if (e != hipSuccess) return e;
-            wide_ws_bytes = wstride * (size_t)wslots;
-        }
-        if (timers) fprintf(stderr, "[gap batch] %s form: %zu jobs, widest %d sequences x %d columns: %zu B of LDS per workgroup of %d threads (rows, trace-back and profile sums in the workspace), 1 per CU, %lld slots, %.1f MB of workspace\n",
-                            tall ? "long-tall" : "long", nj, wn, wc, dyn, kLongThreads, (long long)wslots, (double)(wstride * (size_t)wslots) / 1048576.0);
-        Params P{dev_jobs, (int64_t)nj, d_off, d_chars, d_out, dev_cols, counter, d_wide_ws, (int64_t)wstride, wn, wc, 1, 1, dbg, d_prof};
-        Timed t{nullptr, nullptr, tall ? 4 : 3};
-        if (stats && (e = mark(&t.a)) != hipSuccess) return e;
-        hipLaunchKernelGGL(kernel, dim3((unsigned)wslots), dim3(kLongThreads), dyn, stream, P);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        if (stats) { if ((e = mark(&t.b)) != hipSuccess) return e; timed.push_back(t); }
-        return hipSuccess;
+    // ... sized by the jobs it is given (host_jobs: the same jobs in host memory)
+    auto launch_sized = [&](Form form, const Job* host_jobs, size_t nj, const Job* dev_jobs, int32_t* dev_cols, unsigned long long* counter) -> hipError_t {
+        int wn, wc;
+        extent(form, host_jobs, nj, &wn, &wc);
+        return launch(form, size_launch(form, wn, wc, nj, prop.multiProcessorCount, place), shared_ws, nj, dev_jobs, dev_cols, counter);
     };
     std::vector<int32_t> got(jobs.size());
     std::vector<Job> again; std::vector<size_t> again_at; std::vector<int32_t> again_got;
     std::vector<std::pair<int64_t, int64_t>> spans;
     for (int g = 0; g < n_groups; g++) {
-        const size_t j0 = first[(size_t)g * kForms], jw = first[(size_t)g * kForms + 1], jt = first[(size_t)g * kForms + 2], jl = first[(size_t)g * kForms + 3],
-                     jx = first[(size_t)g * kForms + 4], j1 = first[(size_t)g * kForms + 5];
+        const size_t* at = first.data() + (size_t)g * kForms;      // form f of the group: jobs [at[f], at[f + 1])
+        const size_t j0 = at[0], jw = at[kNarrow + 1], j1 = at[kForms];
         if (j1 > j0) {
-            if (jw > j0) {
-                // a group's jobs: their own queue counter, their slice of the job and column arrays; workspace and slots shared
-                Params P{d_jobs + j0, (int64_t)(jw - j0), d_off, d_chars, d_out, d_cols + j0, d_next + kCounters * g, d_ws, (int64_t)stride, nmax, cap, 0, 0, dbg, d_prof};
-                const int64_t gslots = std::min<int64_t>((int64_t)(jw - j0), slots);
-                Timed t{nullptr, nullptr, 0};
-                if (stats) GA_CHECK(mark(&t.a));
-                hipLaunchKernelGGL(gap_align_kernel<Shared>, dim3((unsigned)gslots), dim3(64), rows_lds, stream, P);
-                GA_CHECK(hipGetLastError());
-                if (stats) { GA_CHECK(mark(&t.b)); timed.push_back(t); }
-            }
-            if (jt > jw) GA_CHECK(launch_wide(1, jobs.data() + jw, jt - jw, d_jobs + jw, d_cols + jw, d_next + kCounters * g + 1));
-            if (jl > jt) GA_CHECK(launch_wide(2, jobs.data() + jt, jl - jt, d_jobs + jt, d_cols + jt, d_next + kCounters * g + 3));
-            if (jx > jl) GA_CHECK(launch_long(false, jobs.data() + jl, jx - jl, d_jobs + jl, d_cols + jl, d_next + kCounters * g + 4));
-            if (j1 > jx) GA_CHECK(launch_long(true, jobs.data() + jx, j1 - jx, d_jobs + jx, d_cols + jx, d_next + kCounters * g + 5));
+            // a form's jobs of a group: their own queue counter, their slice of the job and column arrays; workspace and slots shared
+            unsigned long long* counters = d_next + kCounters * g;
+            if (jw > j0) GA_CHECK(launch(kNarrow, narrow, narrow_ws, jw - j0, d_jobs + j0, d_cols + j0, counters + kFormTable[kNarrow].counter));
+            for (int f = kWide; f < kForms; f++)
+                if (at[f + 1] > at[f]) GA_CHECK(launch_sized((Form)f, jobs.data() + at[f], at[f + 1] - at[f], d_jobs + at[f], d_cols + at[f], counters + kFormTable[f].counter));
             GA_CHECK(hipMemcpyAsync(got.data() + j0, d_cols + j0, 4 * (j1 - j0), hipMemcpyDeviceToHost, stream));
-            if (!wide) GA_CHECK(hipStreamSynchronize(stream));
-            if (wide) {
+            GA_CHECK(hipStreamSynchronize(stream));
+            if (!rect.narrow_only) {
                 // what the narrow form declined although its rows may be wider than the narrow form's columns: once more, wide
-                GA_CHECK(hipStreamSynchronize(stream));
                 again.clear(); again_at.clear();
                 for (size_t i = j0; i < jw; i++) if (got[i] < 0 && jobs[i].max_cols > kMaxCols) { again.push_back(jobs[i]); again_at.push_back(i); }
                 if (!again.empty()) {
                     if (!d_again) { GA_CHECK(dalloc(sizeof(Job) * jobs.size(), (void**)&d_again)); GA_CHECK(dalloc(4 * jobs.size(), (void**)&d_again_cols)); }
                     GA_CHECK(hipMemcpyAsync(d_again, again.data(), sizeof(Job) * again.size(), hipMemcpyHostToDevice, stream));
-                    GA_CHECK(launch_wide(1, again.data(), again.size(), d_again, d_again_cols, d_next + kCounters * g + 2));
+                    GA_CHECK(launch_sized(kWide, again.data(), again.size(), d_again, d_again_cols, counters + kWideAgain));
                     again_got.resize(again.size());
                     GA_CHECK(hipMemcpyAsync(again_got.data(), d_again_cols, 4 * again.size(), hipMemcpyDeviceToHost, stream));
                     GA_CHECK(hipStreamSynchronize(stream));
-                    for (size_t k = 0; k < again.size(); k++) { got[again_at[k]] = again_got[k]; if (stats && again_got[k] >= 0) { stats->jobs_wide++; stats->jobs_narrow--; } }
+                    for (size_t k = 0; k < again.size(); k++) { got[again_at[k]] = again_got[k]; if (stats && again_got[k] >= 0) { stats->jobs[kWide]++; stats->jobs[kNarrow]--; } }
                 }
             }
             // the rows of the group: the areas of its ALIGNED jobs, neighbours in one copy (one copy for a group without a declined
@@ -1885,15 +1776,13 @@ int align_groups(int level, int device, int64_t n_jobs, const int32_t* n_seqs, c
                 a = b;
             }
             GA_CHECK(hipStreamSynchronize(stream));
-            for (size_t i = j0; i < j1; i++) cols[which[i]] = got[i];
-            if (stats) { for (size_t i = j0; i < jw; i++) stats->jobs_narrow += got[i] >= 0; for (size_t i = jw; i < jt; i++) stats->jobs_wide += got[i] >= 0;
-                         for (size_t i = jt; i < jl; i++) stats->jobs_tall += got[i] >= 0; for (size_t i = jl; i < jx; i++) stats->jobs_long += got[i] >= 0;
-                         for (size_t i = jx; i < j1; i++) stats->jobs_long_tall += got[i] >= 0; }
+            for (size_t i = j0; i < j1; i++) cols[plan.which[i]] = got[i];
+            if (stats) for (int f = 0; f < kForms; f++) for (size_t i = at[f]; i < at[f + 1]; i++) stats->jobs[f] += got[i] >= 0;
         }
         if (timers) { char what[32]; snprintf(what, sizeof what, "group %d", g + 1); lap(what); }
         if (done) done(ctx, g);
     }
-    for (const Timed& t : timed) { float ms = 0; if (hipEventElapsedTime(&ms, t.a, t.b) == hipSuccess) (t.form == 4 ? stats->ms_long_tall : t.form == 3 ? stats->ms_long : (t.form == 2 ? stats->ms_tall : (t.form ? stats->ms_wide : stats->ms_narrow))) += (double)ms; }
+    for (const Timed& t : timed) { float ms = 0; if (hipEventElapsedTime(&ms, t.a, t.b) == hipSuccess) stats->ms[t.form] += (double)ms; }
     count_declined();
     if (d_prof) {
         unsigned long long prof[kProfStages];
@@ -1911,78 +1800,59 @@ int align_groups(int level, int device, int64_t n_jobs, const int32_t* n_seqs, c
 #undef GA_CHECK
     return PM_OK;
 }
+int limits_of(Form f, int* max_seqs, int* max_seq_len, int* max_cols) {
+    if (max_seqs) *max_seqs = kFormTable[f].seqs;
+    if (max_seq_len) *max_seq_len = kFormTable[f].seq;
+    if (max_cols) *max_cols = kFormTable[f].cols;
+    return PM_OK;
+}
 }  // namespace
 
-extern "C" int pm_gap_align_batch(int device, int64_t n_jobs, const int32_t* n_seqs, const int64_t* seq_off, const uint8_t* chars,
-                                  const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols) {
-    return align_groups(0, device, n_jobs, n_seqs, seq_off, chars, max_cols, row_off, out_rows, out_bytes, cols, 1, &n_jobs, nullptr, nullptr, nullptr);
+// every entry point takes the same batch and differs in its rectangle (and in which of the forms' counts its stats struct holds)
+#define GA_BATCH_ARGS int device, int64_t n_jobs, const int32_t* n_seqs, const int64_t* seq_off, const uint8_t* chars, \
+                      const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols
+#define GA_GROUP_ARGS GA_BATCH_ARGS, int n_groups, const int64_t* group_end, void (*done)(void* ctx, int group), void* ctx
+#define GA_CALL(form_, stats_) align_groups(rect_of(form_), device, n_jobs, n_seqs, seq_off, chars, max_cols, row_off, out_rows, out_bytes, cols, n_groups, group_end, done, ctx, stats_)
+extern "C" int pm_gap_align_batch(GA_BATCH_ARGS) {
+    return align_groups(rect_of(kNarrow), device, n_jobs, n_seqs, seq_off, chars, max_cols, row_off, out_rows, out_bytes, cols, 1, &n_jobs, nullptr, nullptr, nullptr);
 }
 // The same batch in groups of consecutive jobs (group g = jobs [group_end[g-1], group_end[g])): everything is uploaded once,
 // the groups are aligned one after the other, and when the rows and column counts of a group are in the caller's memory
 // `done(ctx, g)` is called (from this thread) -- the caller can start using them while the later groups are still running.
-extern "C" int pm_gap_align_groups(int device, int64_t n_jobs, const int32_t* n_seqs, const int64_t* seq_off, const uint8_t* chars,
-                                   const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols,
-                                   int n_groups, const int64_t* group_end, void (*done)(void* ctx, int group), void* ctx) {
-    return align_groups(0, device, n_jobs, n_seqs, seq_off, chars, max_cols, row_off, out_rows, out_bytes, cols, n_groups, group_end, done, ctx, nullptr);
-}
+extern "C" int pm_gap_align_groups(GA_GROUP_ARGS) { return GA_CALL(kNarrow, nullptr); }
 // ... and with the wide form: the limits of pm_gap_limits(1, ...)
-extern "C" int pm_gap_align_groups_wide(int device, int64_t n_jobs, const int32_t* n_seqs, const int64_t* seq_off, const uint8_t* chars,
-                                        const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols,
-                                        int n_groups, const int64_t* group_end, void (*done)(void* ctx, int group), void* ctx, pm_gap_stats* stats) {
+extern "C" int pm_gap_align_groups_wide(GA_GROUP_ARGS, pm_gap_stats* stats) {
     FormStats all;
-    const int rc = align_groups(1, device, n_jobs, n_seqs, seq_off, chars, max_cols, row_off, out_rows, out_bytes, cols, n_groups, group_end, done, ctx, stats ? &all : nullptr);
-    if (stats) *stats = pm_gap_stats{all.jobs_narrow, all.jobs_wide, all.declined, all.ms_narrow, all.ms_wide};
+    const int rc = GA_CALL(kWide, stats ? &all : nullptr);
+    if (stats) *stats = pm_gap_stats{all.jobs[kNarrow], all.jobs[kWide], all.declined, all.ms[kNarrow], all.ms[kWide]};
     return rc;
 }
 // ... and with the tall form: the limits of pm_gap_limits_tall
-extern "C" int pm_gap_align_groups_tall(int device, int64_t n_jobs, const int32_t* n_seqs, const int64_t* seq_off, const uint8_t* chars,
-                                        const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols,
-                                        int n_groups, const int64_t* group_end, void (*done)(void* ctx, int group), void* ctx, pm_gap_tall_stats* stats) {
+extern "C" int pm_gap_align_groups_tall(GA_GROUP_ARGS, pm_gap_tall_stats* stats) {
     FormStats all;
-    const int rc = align_groups(2, device, n_jobs, n_seqs, seq_off, chars, max_cols, row_off, out_rows, out_bytes, cols, n_groups, group_end, done, ctx, stats ? &all : nullptr);
-    if (stats) *stats = pm_gap_tall_stats{all.jobs_narrow, all.jobs_wide, all.jobs_tall, all.declined, all.ms_narrow, all.ms_wide, all.ms_tall};
+    const int rc = GA_CALL(kTall, stats ? &all : nullptr);
+    if (stats) *stats = pm_gap_tall_stats{all.jobs[kNarrow], all.jobs[kWide], all.jobs[kTall], all.declined, all.ms[kNarrow], all.ms[kWide], all.ms[kTall]};
     return rc;
 }
 // ... and with the long form: the limits of pm_gap_limits_long
-extern "C" int pm_gap_align_groups_long(int device, int64_t n_jobs, const int32_t* n_seqs, const int64_t* seq_off, const uint8_t* chars,
-                                        const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols,
-                                        int n_groups, const int64_t* group_end, void (*done)(void* ctx, int group), void* ctx, pm_gap_long_stats* stats) {
+extern "C" int pm_gap_align_groups_long(GA_GROUP_ARGS, pm_gap_long_stats* stats) {
     FormStats all;
-    const int rc = align_groups(3, device, n_jobs, n_seqs, seq_off, chars, max_cols, row_off, out_rows, out_bytes, cols, n_groups, group_end, done, ctx, stats ? &all : nullptr);
-    if (stats) *stats = pm_gap_long_stats{all.jobs_narrow, all.jobs_wide, all.jobs_long, all.declined, all.ms_narrow, all.ms_wide, all.ms_long};
+    const int rc = GA_CALL(kLong, stats ? &all : nullptr);
+    if (stats) *stats = pm_gap_long_stats{all.jobs[kNarrow], all.jobs[kWide], all.jobs[kLong], all.declined, all.ms[kNarrow], all.ms[kWide], all.ms[kLong]};
     return rc;
 }
 // ... and with the long-tall form beside the other four: the limits of pm_gap_limits_long_tall
-extern "C" int pm_gap_align_groups_long_tall(int device, int64_t n_jobs, const int32_t* n_seqs, const int64_t* seq_off, const uint8_t* chars,
-                                             const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols,
-                                             int n_groups, const int64_t* group_end, void (*done)(void* ctx, int group), void* ctx, pm_gap_long_tall_stats* stats) {
+extern "C" int pm_gap_align_groups_long_tall(GA_GROUP_ARGS, pm_gap_long_tall_stats* stats) {
     FormStats all;
-    const int rc = align_groups(4, device, n_jobs, n_seqs, seq_off, chars, max_cols, row_off, out_rows, out_bytes, cols, n_groups, group_end, done, ctx, stats ? &all : nullptr);
-    if (stats) *stats = pm_gap_long_tall_stats{all.jobs_narrow, all.jobs_wide, all.jobs_tall, all.jobs_long, all.jobs_long_tall, all.declined,
-                                               all.ms_narrow, all.ms_wide, all.ms_tall, all.ms_long, all.ms_long_tall};
+    const int rc = GA_CALL(kLongTall, stats ? &all : nullptr);
+    if (stats) *stats = pm_gap_long_tall_stats{all.jobs[kNarrow], all.jobs[kWide], all.jobs[kTall], all.jobs[kLong], all.jobs[kLongTall], all.declined,
+                                               all.ms[kNarrow], all.ms[kWide], all.ms[kTall], all.ms[kLong], all.ms[kLongTall]};
     return rc;
 }
-extern "C" int pm_gap_limits_long_tall(int* max_seqs, int* max_seq_len, int* max_cols) {
-    if (max_seqs) *max_seqs = kLongTallSeqs;
-    if (max_seq_len) *max_seq_len = kLongSeq;
-    if (max_cols) *max_cols = kLongCols;
-    return PM_OK;
-}
-extern "C" int pm_gap_limits_long(int* max_seqs, int* max_seq_len, int* max_cols) {
-    if (max_seqs) *max_seqs = kLongSeqs;
-    if (max_seq_len) *max_seq_len = kLongSeq;
-    if (max_cols) *max_cols = kLongCols;
-    return PM_OK;
-}
-extern "C" int pm_gap_limits_tall(int* max_seqs, int* max_seq_len, int* max_cols) {
-    if (max_seqs) *max_seqs = kTallSeqs;
-    if (max_seq_len) *max_seq_len = kWideSeq;
-    if (max_cols) *max_cols = kWideCols;
-    return PM_OK;
-}
-extern "C" int pm_gap_limits(int wide, int* max_seqs, int* max_seq_len, int* max_cols) {
-    if (max_seqs) *max_seqs = kMaxSeqs;
-    if (max_seq_len) *max_seq_len = wide ? kWideSeq : kMaxCols;
-    if (max_cols) *max_cols = wide ? kWideCols : kMaxCols;
-    return PM_OK;
-}
+extern "C" int pm_gap_limits_long_tall(int* max_seqs, int* max_seq_len, int* max_cols) { return limits_of(kLongTall, max_seqs, max_seq_len, max_cols); }
+extern "C" int pm_gap_limits_long(int* max_seqs, int* max_seq_len, int* max_cols) { return limits_of(kLong, max_seqs, max_seq_len, max_cols); }
+extern "C" int pm_gap_limits_tall(int* max_seqs, int* max_seq_len, int* max_cols) { return limits_of(kTall, max_seqs, max_seq_len, max_cols); }
+extern "C" int pm_gap_limits(int wide, int* max_seqs, int* max_seq_len, int* max_cols) { return limits_of(wide ? kWide : kNarrow, max_seqs, max_seq_len, max_cols); }
+#undef GA_CALL
+#undef GA_GROUP_ARGS
+#undef GA_BATCH_ARGS

@@ -131,23 +131,10 @@ void build_rows(const Aligner& a, const Lcb& ct, const std::vector<std::pair<siz
 }  // namespace
 
 }  // namespace parsnp
-// The device gap aligner's wide form (include/parsnp_mum.h).  Weak: a provider of the ABI without it (the CPU providers of the
-// test builds, an older engine library) still links, and the writer then uses pm_gap_align_groups with its narrow limits.
-extern "C" int pm_gap_align_groups_wide(int device, int64_t n_jobs, const int32_t* n_seqs, const int64_t* seq_off, const uint8_t* chars,
-                                        const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols,
-                                        int n_groups, const int64_t* group_end, void (*done)(void* ctx, int group), void* ctx, pm_gap_stats* stats) __attribute__((weak));
-extern "C" int pm_gap_limits(int wide, int* max_seqs, int* max_seq_len, int* max_cols) __attribute__((weak));
-// ... and its tall form (alignments of 513 to 2 048 genomes), weak in the same way: without it such a run aligns its gaps on the host
-extern "C" int pm_gap_align_groups_tall(int device, int64_t n_jobs, const int32_t* n_seqs, const int64_t* seq_off, const uint8_t* chars,
-                                        const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols,
-                                        int n_groups, const int64_t* group_end, void (*done)(void* ctx, int group), void* ctx, pm_gap_tall_stats* stats) __attribute__((weak));
-extern "C" int pm_gap_limits_tall(int* max_seqs, int* max_seq_len, int* max_cols) __attribute__((weak));
-// ... and its long form (gap strings of 321 to 1 024 bases: a cluster distance d above the default), weak in the same way
-extern "C" int pm_gap_align_groups_long(int device, int64_t n_jobs, const int32_t* n_seqs, const int64_t* seq_off, const uint8_t* chars,
-                                        const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols,
-                                        int n_groups, const int64_t* group_end, void (*done)(void* ctx, int group), void* ctx, pm_gap_long_stats* stats) __attribute__((weak));
-extern "C" int pm_gap_limits_long(int* max_seqs, int* max_seq_len, int* max_cols) __attribute__((weak));
-// ... and its long-tall form (more than 512 sequences AND a gap string of 321 to 1 024 bases), weak in the same way
+// The device gap aligner with all its forms behind one entry point (include/parsnp_mum.h).  Weak: a provider of the ABI without it
+// (the CPU providers of the test builds) still links, and the writer then uses pm_gap_align_groups with its narrow limits.  An
+// engine library with some of the forms but not all of them is not provided for: libparsnp_hip.so and parsnp_core are built
+// from one tree.
 extern "C" int pm_gap_align_groups_long_tall(int device, int64_t n_jobs, const int32_t* n_seqs, const int64_t* seq_off, const uint8_t* chars,
                                              const int32_t* max_cols, const int64_t* row_off, uint8_t* out_rows, int64_t out_bytes, int32_t* cols,
                                              int n_groups, const int64_t* group_end, void (*done)(void* ctx, int group), void* ctx, pm_gap_long_tall_stats* stats) __attribute__((weak));
@@ -297,38 +284,16 @@ void write_output(Aligner& a, const std::string& stem, bool* gap_note) {
         for (long x = len; x-- > 0;) { const char c = U.rcu[(unsigned char)g[pos + x]]; if (c) dst[w++] = c; }
         return w;
     };
-    // The gaps go to the device in ONE batch (pm_gap_align_batch: one wavefront per gap, include/parsnp_mum.h); the few the
-    // device does not take -- outside its limits (pm_gap_limits: 320 bases and 640 columns in its wide form, which covers every
-    // gap of the default d = 300; pm_gap_limits_tall: 2 048 sequences; pm_gap_limits_long: 1 024 bases and 2 048 columns, every gap of
-    // a d up to 1 000; pm_gap_limits_long_tall: both at once), or declined -- are aligned here by the host threads, the widest ones while the
-    // device works on the rest.  PARSNP_HOST_GAPS=1: everything on the host (measurement / tests).
+    // The gaps go to the device in ONE batch (pm_gap_align_groups_long_tall: include/parsnp_mum.h); the few the device does not take
+    // -- outside its limits (pm_gap_limits_long_tall: 2 048 sequences of 1 024 bases, 2 048 columns: every gap of a d up to 1 000),
+    // or declined -- are aligned here by the host threads, the widest ones while the device works on the rest.  The library
+    // gives every job the smallest of its forms that holds it, so a run makes this one call whatever its gaps are.
+    // PARSNP_HOST_GAPS=1: everything on the host (measurement / tests).
     constexpr unsigned kNarrowCols = 96;                  // a gap with a longer string counts as wide (GapCounts::jobs_wide)
     constexpr unsigned kWideLen = 320;                    // ... and one with a string longer than this as long (GapCounts::jobs_long)
-    const bool wide_form = pm_gap_align_groups_wide != nullptr && pm_gap_limits != nullptr;
+    const bool all_forms = pm_gap_align_groups_long_tall != nullptr && pm_gap_limits_long_tall != nullptr;
     int dev_seqs = 512, dev_len = (int)kNarrowCols, dev_cols = (int)kNarrowCols;
-    if (wide_form) pm_gap_limits(1, &dev_seqs, &dev_len, &dev_cols);
-    // more genomes than that (every gap has one string per genome): the tall form, where the provider has it -- same batch, same row
-    // capacities, its own entry point; beyond its limit too, the host
-    const bool tall_form = wide_form && n > (size_t)dev_seqs && pm_gap_align_groups_tall != nullptr && pm_gap_limits_tall != nullptr;
-    if (tall_form) pm_gap_limits_tall(&dev_seqs, &dev_len, &dev_cols);
-    // a gap string beyond the wide form's bases (a cluster distance above the default): the long form, where the provider has it and
-    // the alignment has no more sequences than it takes.  A run without such a gap makes the call it has always made.
-    bool long_form = false;
-    if (wide_form && !tall_form && n <= (size_t)dev_seqs && pm_gap_align_groups_long != nullptr && pm_gap_limits_long != nullptr) {
-        for (long x = 0; x < nj && !long_form; x++) long_form = jobs[(size_t)x].max_len > (unsigned)dev_len;
-        int long_seqs = 0;
-        if (long_form) { pm_gap_limits_long(&long_seqs, nullptr, nullptr); long_form = n <= (size_t)long_seqs; }
-        if (long_form) pm_gap_limits_long(&dev_seqs, &dev_len, &dev_cols);
-    }
-    // both at once -- more genomes than the wide form takes and a gap string beyond its bases: the long-tall form, where the provider
-    // has it.  A run of that many genomes without such a gap calls the tall entry point as it always has.
-    bool long_tall_form = false;
-    if (tall_form && n <= (size_t)dev_seqs && pm_gap_align_groups_long_tall != nullptr && pm_gap_limits_long_tall != nullptr) {
-        for (long x = 0; x < nj && !long_tall_form; x++) long_tall_form = jobs[(size_t)x].max_len > (unsigned)dev_len;
-        int lt_seqs = 0;
-        if (long_tall_form) { pm_gap_limits_long_tall(&lt_seqs, nullptr, nullptr); long_tall_form = n <= (size_t)lt_seqs; }
-        if (long_tall_form) pm_gap_limits_long_tall(&dev_seqs, &dev_len, &dev_cols);
-    }
+    if (all_forms) pm_gap_limits_long_tall(&dev_seqs, &dev_len, &dev_cols);
     static const bool host_gaps = test_hook("PARSNP_HOST_GAPS") != nullptr;
     // The LCBs are cut into a few groups of consecutive LCBs with about the same alignment work, one device batch each:
     // the file offsets of a group's records only depend on the groups before it, so its records are written while the
@@ -442,10 +407,7 @@ void write_output(Aligner& a, const std::string& stem, bool* gap_note) {
     for (auto& pr : batch_done) batch_ready.push_back(pr.get_future());
     const size_t on_device = B.job.size();
     struct Reported { vector<std::promise<int>>* done; size_t n = 0; } reported{&batch_done, 0};
-    pm_gap_stats device_stats{0, 0, 0, 0.0, 0.0};
-    pm_gap_tall_stats tall_stats{0, 0, 0, 0, 0.0, 0.0, 0.0};
-    pm_gap_long_stats long_stats{0, 0, 0, 0, 0.0, 0.0, 0.0};
-    pm_gap_long_tall_stats long_tall_stats{0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    pm_gap_long_tall_stats device_stats{0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0};
     std::future<void> device_side = std::async(std::launch::async, [&] {
         int rc = PM_OK;
         if (!B.job.empty()) {
@@ -453,18 +415,9 @@ void write_output(Aligner& a, const std::string& stem, bool* gap_note) {
             for (size_t g = 0; g < ngroups; g++) group_end[g] = (int64_t)batch[g].y1;
             const double t0 = clock_s();
             auto report = [](void* ctx, int) { Reported* r = (Reported*)ctx; (*r->done)[r->n++].set_value(PM_OK); };
-            if (long_tall_form)
+            if (all_forms)
                 rc = pm_gap_align_groups_long_tall(-1, (int64_t)B.job.size(), B.nseq.data(), B.seqoff.data(), B.chars.data(), B.maxcols.data(), B.rowoff.data(),
-                                                   B.out.data(), (int64_t)B.out.size(), B.cols.data(), (int)ngroups, group_end.data(), report, &reported, &long_tall_stats);
-            else if (tall_form)
-                rc = pm_gap_align_groups_tall(-1, (int64_t)B.job.size(), B.nseq.data(), B.seqoff.data(), B.chars.data(), B.maxcols.data(), B.rowoff.data(),
-                                              B.out.data(), (int64_t)B.out.size(), B.cols.data(), (int)ngroups, group_end.data(), report, &reported, &tall_stats);
-            else if (long_form)
-                rc = pm_gap_align_groups_long(-1, (int64_t)B.job.size(), B.nseq.data(), B.seqoff.data(), B.chars.data(), B.maxcols.data(), B.rowoff.data(),
-                                              B.out.data(), (int64_t)B.out.size(), B.cols.data(), (int)ngroups, group_end.data(), report, &reported, &long_stats);
-            else if (wide_form)
-                rc = pm_gap_align_groups_wide(-1, (int64_t)B.job.size(), B.nseq.data(), B.seqoff.data(), B.chars.data(), B.maxcols.data(), B.rowoff.data(),
-                                              B.out.data(), (int64_t)B.out.size(), B.cols.data(), (int)ngroups, group_end.data(), report, &reported, &device_stats);
+                                                   B.out.data(), (int64_t)B.out.size(), B.cols.data(), (int)ngroups, group_end.data(), report, &reported, &device_stats);
             else
                 rc = pm_gap_align_groups(-1, (int64_t)B.job.size(), B.nseq.data(), B.seqoff.data(), B.chars.data(), B.maxcols.data(), B.rowoff.data(),
                                          B.out.data(), (int64_t)B.out.size(), B.cols.data(), (int)ngroups, group_end.data(), report, &reported);
@@ -852,25 +805,16 @@ void write_output(Aligner& a, const std::string& stem, bool* gap_note) {
         double sum = 0, mx = 0; long arg = 0, on_host = 0;
         for (long x = 0; x < nj; x++) { sum += jt[(size_t)x]; on_host += jobs[(size_t)x].on_host; if (jt[(size_t)x] > mx) { mx = jt[(size_t)x]; arg = x; } }
         gap_counts.host += on_host; gap_counts.host_s += sum;
-        if (long_tall_form) {      // one record for all five forms: handed to the records the counters below read
-            tall_stats = pm_gap_tall_stats{long_tall_stats.jobs_narrow, long_tall_stats.jobs_wide, long_tall_stats.jobs_tall, long_tall_stats.declined,
-                                           long_tall_stats.ms_narrow, long_tall_stats.ms_wide, long_tall_stats.ms_tall};
-            long_stats = pm_gap_long_stats{long_tall_stats.jobs_narrow, long_tall_stats.jobs_wide, long_tall_stats.jobs_long, long_tall_stats.declined,
-                                           long_tall_stats.ms_narrow, long_tall_stats.ms_wide, long_tall_stats.ms_long};
-        }
-        if (tall_form) device_stats = pm_gap_stats{tall_stats.jobs_narrow, tall_stats.jobs_wide, tall_stats.declined, tall_stats.ms_narrow, tall_stats.ms_wide};
-        if (long_form) device_stats = pm_gap_stats{long_stats.jobs_narrow, long_stats.jobs_wide, long_stats.declined, long_stats.ms_narrow, long_stats.ms_wide};
-        if (device_gaps_failed) { device_stats = pm_gap_stats{0, 0, 0, 0.0, 0.0}; tall_stats = pm_gap_tall_stats{0, 0, 0, 0, 0.0, 0.0, 0.0}; long_stats = pm_gap_long_stats{0, 0, 0, 0, 0.0, 0.0, 0.0};
-                                  long_tall_stats = pm_gap_long_tall_stats{0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0}; }
-        else if (!wide_form) device_stats.jobs_narrow = (int64_t)on_device - declined;      // (a provider without the wide form reports nothing)
+        if (device_gaps_failed) device_stats = pm_gap_long_tall_stats{0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        else if (!all_forms) device_stats.jobs_narrow = (int64_t)on_device - declined;      // (a provider with the narrow form alone reports nothing)
         gap_counts.device_narrow = (long)device_stats.jobs_narrow; gap_counts.device_wide = (long)device_stats.jobs_wide;
         gap_counts.device_narrow_ms = device_stats.ms_narrow; gap_counts.device_wide_ms = device_stats.ms_wide;
-        gap_counts.device_tall = (long)tall_stats.jobs_tall; gap_counts.device_tall_ms = tall_stats.ms_tall;
-        gap_counts.device_long = (long)long_stats.jobs_long; gap_counts.device_long_ms = long_stats.ms_long;
-        gap_counts.device_long_tall = (long)long_tall_stats.jobs_long_tall; gap_counts.device_long_tall_ms = long_tall_stats.ms_long_tall;
+        gap_counts.device_tall = (long)device_stats.jobs_tall; gap_counts.device_tall_ms = device_stats.ms_tall;
+        gap_counts.device_long = (long)device_stats.jobs_long; gap_counts.device_long_ms = device_stats.ms_long;
+        gap_counts.device_long_tall = (long)device_stats.jobs_long_tall; gap_counts.device_long_tall_ms = device_stats.ms_long_tall;
         if (dbg && nj)
             fprintf(stderr, "[output] %ld gap alignments: %zu on the device (%lld narrow form in %.1f ms, %lld wide form in %.1f ms, %lld tall form in %.1f ms, %lld long form in %.1f ms, %lld long-tall form in %.1f ms, %ld declined), %.3f s of host work, longest %.3f s (gap of %u columns)\n",
-                    nj, on_device, (long long)device_stats.jobs_narrow, device_stats.ms_narrow, (long long)device_stats.jobs_wide, device_stats.ms_wide, (long long)tall_stats.jobs_tall, tall_stats.ms_tall, (long long)long_stats.jobs_long, long_stats.ms_long, (long long)long_tall_stats.jobs_long_tall, long_tall_stats.ms_long_tall, declined, sum, mx, jobs[(size_t)arg].max_len);
+                    nj, on_device, (long long)device_stats.jobs_narrow, device_stats.ms_narrow, (long long)device_stats.jobs_wide, device_stats.ms_wide, (long long)device_stats.jobs_tall, device_stats.ms_tall, (long long)device_stats.jobs_long, device_stats.ms_long, (long long)device_stats.jobs_long_tall, device_stats.ms_long_tall, declined, sum, mx, jobs[(size_t)arg].max_len);
     }
     if (dbg) {
         long ns = 0, np = 0, nt = 0;

@@ -392,7 +392,7 @@ def lay_out(call):
         off += len(j.block) * j.max_cols
     out_bytes = off - call.short_by
     caps = {}
-    for j in call.jobs:      # the launch's cap: the widest max_cols among the jobs that share the job's form (as launch_wide / launch_long size it)
+    for j in call.jobs:      # the launch's cap: the widest max_cols among the jobs that share the job's form (as extent() of gap_plan.h sizes it)
         f = form_of(j.block)
         caps[f] = max(caps.get(f, 1), min(j.max_cols, LIMITS[f][2]))
     verdict = []

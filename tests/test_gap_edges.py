@@ -17,6 +17,7 @@ from test_gapalign import aligner  # noqa: F401  (fixture: the host restatement)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KERNEL = os.path.join(ROOT, "parsnp_amd", "csrc", "engine", "gapalign_hip.hip")
+PLAN = os.path.join(ROOT, "parsnp_amd", "csrc", "engine", "gap_plan.h")      # the forms' limits, included by the kernel's source
 EMU_SRC = os.path.join(ROOT, "tests", "emu", "gap_emu.cpp")
 EMU_STUB = os.path.join(ROOT, "tests", "emu", "hipstub")
 EMU_LIB = os.path.join(ROOT, "tests", "emu", "libgap_emu.so")
@@ -270,7 +271,7 @@ def test_floor_decline_reasons():
 
 def test_generator_matches_the_kernel():
     """the constants the generator places its edges by, read out of the kernel's source"""
-    src = open(KERNEL).read()
+    src = open(PLAN).read() + open(KERNEL).read()
     got = {}
     for name in gapedges.CONSTANTS:
         m = re.search(r"\bconstexpr int (?:\w+ = \d+, )*%s = (\d+)" % name, src)
@@ -285,14 +286,15 @@ def test_generator_matches_the_kernel():
     assert "in_mask = wave == 0 ? 4095 : kLongRing - 1, out_mask = wave == 3 ? 4095 : kLongRing - 1;" in src
     assert "if (first) em = (uint8_t)(cnt & 255);" in src and "const int c1 = lane, c2 = lane + 64;" in src
     assert got["kLongThreads"] == 4 * 64 and got["kLongChunk"] == 64 and 4 * got["kLongChunk"] == got["kLongRing"]
-    assert "const int form = n > kMaxSeqs ? 2 : (w > kWideSeq ? 3 : (w > kMaxCols ? 1 : 0));" in src
+    # (the routing rule, now route() of gap_plan.h; tests/test_gap_plan.py runs it)
+    assert "return n > kMaxSeqs ? (w > kWideSeq ? kLongTall : kTall) : (w > kWideSeq ? kLong : (w > kMaxCols ? kWide : kNarrow));" in src
 
 
 # ---- the long form, executed on the host
 
 @pytest.fixture(scope="module")
 def emu_long():
-    deps = [EMU_SRC, KERNEL, os.path.join(EMU_STUB, "hip", "hip_runtime.h"), os.path.join(ROOT, "include", "parsnp_mum.h")]
+    deps = [EMU_SRC, KERNEL, PLAN, os.path.join(EMU_STUB, "hip", "hip_runtime.h"), os.path.join(ROOT, "include", "parsnp_mum.h")]
     if not os.path.exists(EMU_LIB) or os.path.getmtime(EMU_LIB) < max(os.path.getmtime(d) for d in deps):
         tmp = EMU_LIB[:-len(".so")] + ".%d.so" % os.getpid()
         subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-w", "-ffp-contract=off", "-I" + EMU_STUB, "-x", "c++", EMU_SRC, "-o", tmp], check=True)

@@ -14,7 +14,7 @@ from parsnp_amd.paths import HIP_LIB
 from test_gap_edges import block_call, run_call
 
 pytestmark = pytest.mark.gpu
-LDS_LIMIT = 160 * 1024 - 1024      # launch_wide's rule: fixed + rows + trace-back <= 160 KB - 1 KB
+LDS_LIMIT = 160 * 1024 - 1024      # size_launch's rule (gap_plan.h): fixed + rows + trace-back <= 160 KB - 1 KB
 
 
 @pytest.fixture(scope="module")
@@ -111,7 +111,7 @@ def _pick(topic, name, max_cols):
 
 def test_wide_placements(lib, monkeypatch, capfd):
     """four launches of the wide form whose widest job puts the rows and the trace-back bytes in each combination of LDS and workspace,
-    by launch_wide's rule (the fixed block is about 54 KB: n x cap bytes of rows beside it up to 159 KB, then (cap + 1)^2 trace-back
+    by size_launch's rule (gap_plan.h) (the fixed block is about 54 KB: n x cap bytes of rows beside it up to 159 KB, then (cap + 1)^2 trace-back
     bytes if they still fit); then the same blocks with PM_GAP_WIDE_PLACE = 1, 2, 3, which force the workspace: same rows"""
     monkeypatch.setenv("PARSNP_DEBUG_TIMERS", "1")
     pairs = [_pick("wide_pairs", "wide 97x127 copy", 200), _pick("wide_pairs", "wide 128x97 straddle0", 180), _pick("wide_pairs", "wide 97x97 unrelated", 199)]
