@@ -1,6 +1,14 @@
 // engine_core.h -- orchestration of one pm_multi_mum_batch call, templated on the execution backend.
 // HipBackend (engine_hip.hip) = the product: HIP kernels on gfx950, one stream, HIP-event timing.
 // tests/emu/ instantiates it with a sequential host backend to check the logic without a GPU (tests only).
+//
+// A search (run -> run_once) is a call record (SearchCall, on run_once's stack: what more than one stage reads, and every host
+// landing target of the call's asynchronous downloads) handed through named stages, each a private member function:
+//   plan_call -> upload_and_clear -> build_index -> count_units -> search_events { event_pass } -> order_events
+//   -> mumi_tail | master_ep -> candidate_tail { tail_attempt { exchange_states, compact_sp | compact_rows } }
+// A stage returns kNext, kRepeat (inside the two loops: a capacity was too small) or the value the call ends with.  run() repeats
+// the whole call for the index rebuild and the suffix-array path.  The words of the counter block are named once (kCtr*), the
+// store's four counters move together (store_mark / store_rewind / store_reset).
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -144,7 +152,6 @@ public:
             }
         }
         words += 8;                              // SmallPairEvents reads a 128-base window + 2 blocks from any position of the last strand
-        total_words = words;
         blk = (SeqBlock*)be.alloc((size_t)words * sizeof(SeqBlock));
         d_goff = (int64_t*)be.alloc(sizeof(int64_t) * 2 * (size_t)n);
         d_glen = (int64_t*)be.alloc(sizeof(int64_t) * (size_t)n);
@@ -190,13 +197,17 @@ public:
         if (dense_all && nreg > 0) { dense_h.assign((size_t)nreg, 1); dense_mode = true; }
         const auto t0 = std::chrono::steady_clock::now();
         index_rebuild = false;
-        int rc = run_once(nreg, starts, lens, minsize, out, want_events, mumi, gb);
-        if (rc == kIndexRebuild) {      // the overflow list of the bucket build was full: the same call, every region built by IndexInsert
-            (void)be.collect();
-            call_ordinal = ordinal;
-            index_rebuild = true;
-            rc = run_once(nreg, starts, lens, minsize, out, want_events, mumi, gb);
-        }
+        auto once = [&] {
+            int rc = run_once(nreg, starts, lens, minsize, out, want_events, mumi, gb);
+            if (rc == kIndexRebuild) {      // the overflow list of the bucket build was full: the same call, every region built by IndexInsert
+                (void)be.collect();
+                call_ordinal = ordinal;
+                index_rebuild = true;
+                rc = run_once(nreg, starts, lens, minsize, out, want_events, mumi, gb);
+            }
+            return rc;
+        };
+        int rc = once();
         if (rc == -5 && budget_exceeded && !dense_mode) {
             budget_retries++;
             last_dense_overrun_ms = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -206,13 +217,7 @@ public:
             (void)be.collect();          // (that pass's phases are not the second run's)
             call_ordinal = ordinal;      // (the same call of the step: the same capacities)
             dense_mode = true; budget_exceeded = false;
-            rc = run_once(nreg, starts, lens, minsize, out, want_events, mumi, gb);
-            if (rc == kIndexRebuild) {
-                (void)be.collect();
-                call_ordinal = ordinal;
-                index_rebuild = true;
-                rc = run_once(nreg, starts, lens, minsize, out, want_events, mumi, gb);
-            }
+            rc = once();
         }
         dense_mode = false; index_rebuild = false;
         return rc;
@@ -227,32 +232,115 @@ public:
     static constexpr int kIndexRebuild = -99;      // run_once: the bucket build's overflow list was full (never leaves run())
     bool index_rebuild = false;                    // this run of the batch builds every region with IndexInsert
     int64_t index_overflow_seen = 0;               // ... after a bucket build that left this many overflow records
+
+    // The counter block of a search (d_counter): kSlices event counters one 64-byte line apart, then these words.  It is cleared and
+    // read back as a whole (round trip 1).
+    static constexpr size_t kCtrBase = (size_t)kSlices * kSliceStride;
+    static constexpr size_t kCtrErr = kCtrBase;             // the error word of the batch (kErr*)
+    static constexpr size_t kCtrGrouped = kCtrBase + 2;     // the block counter of the grouped events
+    static constexpr size_t kCtrWide = kCtrBase + 3;        // the wide form's kCtrWideWords counts: events, regions handed back, regions taken
+    static constexpr size_t kCtrWideWords = 3;
+    static constexpr size_t kCtrOverflow = kCtrBase + 6;    // overflow records of the index's bucket build
+    static constexpr size_t kCtrLost = kCtrBase + 7;        // IndexVerify's count
+    static constexpr size_t kCtrWords = kCtrBase + 8;       // the block's size
+    static_assert(kCtrErr < kCtrGrouped && kCtrGrouped < kCtrWide && kCtrWide + kCtrWideWords <= kCtrOverflow && kCtrOverflow < kCtrLost && kCtrLost < kCtrWords,
+                  "the words of the counter block are distinct and inside it");
+
+private:
+    // what call number `i` of the last step needed (i = 0: the anchor call; then the searches of store regions in their order): the
+    // capacities call i of this step launches over instead of waiting for its counts
+    struct CallHint { int64_t units = 0, ncand = 0, nok = 0; };
+    // the four counters of the MUM store and the region store that a search may move, as one thing: store_mark() before the tail
+    // of a call writes rows, store_rewind() when that tail is repeated, store_reset() when an anchor call begins a new store
+    struct StoreCounts { int64_t ms_count, rg_count, layout_rows, rg_pkey_init; };
+    StoreCounts store_mark() const { return StoreCounts{ms_count, rg_count, layout_rows, rg_pkey_init}; }
+    void store_rewind(const StoreCounts& m) { ms_count = m.ms_count; rg_count = m.rg_count; layout_rows = m.layout_rows; rg_pkey_init = m.rg_pkey_init; }
+    void store_reset() { store_rewind(StoreCounts{0, 0, -1, 0}); }      // (a new region store: none of its regions has been processed)
+
+    // One search call (run_once): what more than one of its stages reads.  It lives on run_once's stack for the whole call, and EVERY
+    // host landing target of an asynchronous download of the call is a member of it (the last group; alg_sets is the engine's own):
+    // however a stage returns between a d2h_async and the wait that fills its target, the target outlives that wait.
+    struct SearchCall {
+        // the arguments
+        const int64_t nreg; const int64_t* const starts; const int64_t* const lens; const int32_t* const minsize; BatchResult* const out;
+        const bool want_events, mumi; const GapBatch* const gb;
+        bool from_store = false;      // the rows are regions of the region store: the host never sees them
+        // geometry (plan_call; nwv and d_err: upload_and_clear)
+        int nq = 0, no_small = 0, lbits = 0;
+        size_t nrow = 0, regz = 0, bytes_R = 0, bytes_pre = 0;
+        int64_t npairs = 0, npos = 0, tsize = 0, fwords = 0, tsize_clear = 0, fwords_clear = 0, nbk = 0, npos_bucketed = 0, nchunks = 0, centries = 0, nwv = 0;
+        // the page-locked parameter block  [ RegionInfo x nreg | posbase | cbase | starts rows | lens rows ], the first bucket of every region
+        RegionInfo* R = nullptr; int64_t *posbase = nullptr, *cbase = nullptr, *stage = nullptr;
+        std::vector<int64_t> bbase;
+        uint32_t* d_err = nullptr;        // the error word of the counter block
+        // index: regions flagged for the suffix-array path, capacity of the bucket build's overflow list, its counts were read
+        int64_t nflag = 0; uint64_t ovf_cap = 0; bool index_counts_read = false;
+        // event search: the hints of this call of the step, capacities and live counts
+        CallHint none; CallHint* hint = nullptr;
+        int64_t nunits = 0; bool units_known = false;
+        size_t ev_guess = 0, slice_cap = 0, queue_cap = 0, grp_cap = 0;
+        uint64_t nev = 0, nrest = 0, ngrp = 0, worst_slice = 0;
+        uint32_t errbits = 0, sticky = 0;
+        bool first_form = false, wide_form = false, grouping = false, by_buckets = false, sharded = false;
+        uint64_t *skey = nullptr, *sval = nullptr;      // the events in order
+        // candidate tail: where the device keeps the candidate count; the call looks like an anchor call
+        const int64_t* ncand_p = nullptr; bool anchor_guess = false;
+        // ... and its current attempt: counts waited for (exact) or capacities, where the device keeps the accepted count
+        bool exact = false, anchor_call = false;
+        int64_t ncand_i = 0, nok = 0; uint64_t ncand = 0; size_t nokz = 0; const int64_t* nok_p = nullptr;
+        // landing targets of asynchronous downloads
+        std::vector<uint64_t> counts, qcounts; int64_t nunits_live = 0;      // search_events: round trip 1
+        int32_t verdict = 0;                                                  // master_ep: read with the candidate count
+        std::vector<int32_t> reg_h; int64_t counts_h[2] = {0, 0};             // candidate_tail: round trip 4
+    };
+    // what a stage returns: a value <= 0 ends the call with it (0: done, nothing more to do; < 0: an error code), else
+    static constexpr int kNext = 1, kRepeat = 2;      // go on with the next stage; the stage's loop goes round again
+
+    // The stages, in order: plan_call (host only), upload_and_clear, build_index, count_units (waits for the unit count unless a hint
+    // stands in), search_events (round trip 1, once per pass), order_events, then mumi_tail (waits, ends the call) or master_ep and
+    // candidate_tail (round trips 2-4; with fast_tail the last one only).
     int run_once(int64_t nreg, const int64_t* starts, const int64_t* lens, const int32_t* minsize, BatchResult* out, bool want_events,
                  bool mumi, const GapBatch* gb = nullptr) {
+        SearchCall c{nreg, starts, lens, minsize, out, want_events, mumi, gb};
+        int rc = plan_call(c);
+        if (rc != kNext) return rc;
+        upload_and_clear(c);
+        if ((rc = build_index(c)) != kNext) return rc;
+        if ((rc = count_units(c)) != kNext) return rc;
+        if ((rc = search_events(c)) != kNext) return rc;
+        order_events(c);
+        if (mumi) return mumi_tail(c);
+        if ((rc = master_ep(c)) != kNext) return rc;
+        return candidate_tail(c);
+    }
+
+    int plan_call(SearchCall& c) {
+        const int64_t nreg = c.nreg; const int64_t* const starts = c.starts; const int64_t* const lens = c.lens; const int32_t* const minsize = c.minsize;
+        BatchResult* const out = c.out; const GapBatch* const gb = c.gb;
         timing.clear();
-        const int nq = ngen - 1;
+        const int nq = c.nq = ngen - 1;
         out->nregions = nreg; out->nq = nq; out->total = 0;
         out->off.assign((size_t)nreg + 1, 0);
         out->release();
         out->pool = pool;
         if (nreg == 0) return 0;
         if (nq < 1) { error = "need at least one query genome"; return -2; }
-        const int no_small = mumi ? 1 : 0;
+        const int no_small = c.no_small = c.mumi ? 1 : 0;
 
         // -- host: the page-locked parameter block  [ RegionInfo x nreg | posbase | cbase | starts rows | lens rows ]
         // (regions of the region store: the rows part holds their ids only)
-        const size_t nrow = (size_t)nreg * (size_t)ngen;
-        const size_t regz = (size_t)nreg;
-        const size_t bytes_R = sizeof(RegionInfo) * regz, bytes_pre = 8 * (regz + 1);
-        const bool from_store = gb && gb->store_ids;
+        const size_t nrow = c.nrow = (size_t)nreg * (size_t)ngen;
+        const size_t regz = c.regz = (size_t)nreg;
+        const size_t bytes_R = c.bytes_R = sizeof(RegionInfo) * regz, bytes_pre = c.bytes_pre = 8 * (regz + 1);
+        const bool from_store = c.from_store = gb && gb->store_ids;
         if (gb && !from_store) { error = "bad region list"; return -2; }
         const size_t nrow_staged = gb ? 0 : nrow;
         uint8_t* block = (uint8_t*)be.staging(bytes_R + 2 * bytes_pre + 16 * nrow_staged + (gb ? 4 * regz : 0) + 64);
         if (!block) { error = "cannot allocate the request staging block"; return -3; }
-        RegionInfo* R = (RegionInfo*)block;
-        int64_t* posbase = (int64_t*)(block + bytes_R);
-        int64_t* cbase = posbase + regz + 1;
-        int64_t* stage = cbase + regz + 1;
+        RegionInfo* R = c.R = (RegionInfo*)block;
+        int64_t* posbase = c.posbase = (int64_t*)(block + bytes_R);
+        int64_t* cbase = c.cbase = posbase + regz + 1;
+        int64_t* stage = c.stage = cbase + regz + 1;
         std::vector<size_t> guess_r(regz, 0);
         std::vector<int64_t> units_r(regz, 0);
         if (from_store) {
@@ -306,12 +394,13 @@ public:
             if (b & 1) { error = "region outside its genome"; return -2; }
             if (b & 2) { error = "region longer than 2^31"; return -5; }
         }
-        int64_t npos = 0, tsize = 0, fwords = 0, nunits = 0;
-        int64_t tsize_b = 0, fwords_b = 0, nbk = 0, npos_bucketed = 0;      // of the regions built by buckets: slots, filter words, buckets, positions
-        std::vector<int64_t> bbase(regz + 1, 0);                            // first bucket of every region
+        int64_t &npos = c.npos, &tsize = c.tsize, &fwords = c.fwords, &nunits = c.nunits;      // (all 0)
+        int64_t tsize_b = 0, fwords_b = 0, &nbk = c.nbk, &npos_bucketed = c.npos_bucketed;     // of the regions built by buckets: slots, filter words, buckets, positions
+        std::vector<int64_t>& bbase = c.bbase;                                                 // first bucket of every region
+        bbase.assign(regz + 1, 0);
         const bool by_index_buckets = index_build && !index_rebuild;
         int32_t max_nr = 1;
-        size_t ev_guess = 1 << 16;     // first-call event buffer: a match of length >= minsize every max(8,minsize) bases is generous
+        size_t& ev_guess = c.ev_guess = 1 << 16;     // first-call event buffer: a match of length >= minsize every max(8,minsize) bases is generous
         cbase[0] = 0;
         for (int64_t r = 0; r < nreg; r++) {
             RegionInfo& ri = R[(size_t)r];
@@ -346,23 +435,32 @@ public:
         }
         posbase[regz] = npos;
         bbase[regz] = nbk;
-        const int64_t tsize_clear = tsize, fwords_clear = fwords;
+        const int64_t tsize_clear = c.tsize_clear = tsize, fwords_clear = c.fwords_clear = fwords;
         for (int64_t r = 0; r < nreg; r++) {
             RegionInfo& ri = R[(size_t)r];
             if (ri.tbase < 0) { ri.tbase = tsize_clear + (-1 - ri.tbase); ri.fbase = fwords_clear + (-1 - ri.fbase); }
         }
         tsize += tsize_b; fwords += fwords_b;
-        last_index_bucketed = npos_bucketed; last_index_overflow = index_rebuild ? index_overflow_seen : 0; last_index_lost = -1;
-        last_positions = npos; last_candidates = 0; last_accepted = 0; last_grouped = 0; last_grouped_wide = 0; last_handed_back = -1; last_wide_regions = 0;
-        const int64_t npairs = nreg * nq;
-        const int64_t nchunks = cbase[regz] - nreg;                  // 256-position chunks of the batch
-        const int64_t centries = cbase[regz] * nq;
-        const int lbits = bits_for((uint64_t)max_nr);
+        reset_call_counts();      // (last_events and last_rest stand until the event search of this call has counted)
+        last_index_bucketed = npos_bucketed; last_index_overflow = index_rebuild ? index_overflow_seen : 0;
+        last_positions = npos;
+        const int64_t npairs = c.npairs = nreg * nq;
+        c.nchunks = cbase[regz] - nreg;                  // 256-position chunks of the batch
+        const int64_t centries = c.centries = cbase[regz] * nq;
+        const int lbits = c.lbits = bits_for((uint64_t)max_nr);
         if (bits_for((uint64_t)npairs) + lbits + 1 > 64) { error = "batch too large for 64-bit event keys"; return -5; }
         if (npairs >= (1ll << 31) || nreg >= (1ll << 31)) { error = "too many regions in one batch"; return -5; }
         if (nunits >= (1ll << 31)) { error = "too many work units in one batch"; return -5; }
         if (centries >= (1ll << 31)) { error = "coarse event index too large"; return -5; }
+        return kNext;
+    }
 
+    void upload_and_clear(SearchCall& c) {
+        const int64_t nreg = c.nreg, npos = c.npos, tsize = c.tsize, fwords = c.fwords, tsize_clear = c.tsize_clear, fwords_clear = c.fwords_clear, npairs = c.npairs, centries = c.centries;
+        const int nq = c.nq;
+        const size_t nrow = c.nrow, regz = c.regz, bytes_R = c.bytes_R, bytes_pre = c.bytes_pre;
+        const GapBatch* const gb = c.gb; const bool from_store = c.from_store;
+        RegionInfo* const R = c.R; int64_t* const posbase = c.posbase; int64_t* const cbase = c.cbase; int64_t* const stage = c.stage;
         be.mark("setup");
         ensure(d_R, regz);
         ensure(d_starts, nrow); ensure(d_lens, nrow);
@@ -379,9 +477,8 @@ public:
             be.launch("gather_regions", (int64_t)nrow, GatherRegions{d_list.p, ngen, d_rg_start.p, d_rg_len.p, d_starts.p, d_lens.p});
         }
         // event counters: kSlices counters one 64-byte line apart, then the error word of the batch (read back together)
-        const size_t ncounter = (size_t)kSlices * kSliceStride + 8;
-        ensure(d_counter, ncounter);
-        uint32_t* d_err = (uint32_t*)(d_counter.p + (size_t)kSlices * kSliceStride);
+        ensure(d_counter, kCtrWords);
+        uint32_t* d_err = c.d_err = (uint32_t*)(d_counter.p + kCtrErr);
 
         // -- reference index + repeat lengths
         ensure(d_slots, (size_t)tsize); ensure(d_filter, (size_t)fwords);
@@ -389,24 +486,23 @@ public:
         ensure(d_epm, (size_t)std::max<int64_t>(npos, 1) + 1);     // + the verdict word of a sharded run
         // everything the call clears before it starts, in one launch: presence filter, slots (0xff = empty), event counters + error
         // word, the repeated-K-mer bits, the coarse index, the closing words of the two prefix scans, the byte counters
-        const int64_t nwv = (npos + 63) / 64;
-        const bool from_store_ = gb && gb->store_ids;
+        const int64_t nwv = c.nwv = (npos + 63) / 64;
         ensure(d_repeated, (size_t)(npos / 32 + 2));       // (SeedExtend reads the word after a position's own)
         ensure(d_ucount, (size_t)npairs + 1); ensure(d_uoff, (size_t)npairs + 1);
         ensure(d_coarse, (size_t)std::max<int64_t>(centries, 1));
         ensure(d_wmask, (size_t)nwv + 1); ensure(d_wcount, (size_t)nwv + 1); ensure(d_woff, (size_t)nwv + 1);
-        if (from_store_) ensure(d_alg, 8 * (size_t)kAlgSets);
+        if (from_store) ensure(d_alg, 8 * (size_t)kAlgSets);
         ensure(d_dense, regz);
         {
             // (the regions' dense flags as well -- but in the suffix-array run, which sets them from the host below)
             const ClearJob jobs[] = {
-                {d_filter.p, sizeof(uint32_t) * (size_t)fwords_clear, 0}, {d_slots.p, sizeof(uint64_t) * (size_t)tsize_clear, 0xff}, {d_counter.p, 8 * ncounter, 0},
+                {d_filter.p, sizeof(uint32_t) * (size_t)fwords_clear, 0}, {d_slots.p, sizeof(uint64_t) * (size_t)tsize_clear, 0xff}, {d_counter.p, 8 * kCtrWords, 0},
                 {d_repeated.p, 4 * (size_t)(npos / 32 + 2), 0}, {d_coarse.p, 4 * (size_t)std::max<int64_t>(centries, 1), 0},
-                {d_ucount.p + npairs, 8, 0}, {d_wcount.p + nwv, 8, 0}, {from_store_ ? d_alg.p : nullptr, from_store_ ? (size_t)64 * kAlgSets : 0, 0},
+                {d_ucount.p + npairs, 8, 0}, {d_wcount.p + nwv, 8, 0}, {from_store ? d_alg.p : nullptr, from_store ? (size_t)64 * kAlgSets : 0, 0},
                 {dense_mode ? nullptr : d_dense.p, dense_mode ? 0 : regz, 0}};
             be.clear_many(jobs, (int)(sizeof jobs / sizeof jobs[0]));
         }
-        int64_t nflag = 0;      // the suffix-array run: regions flagged (by the pass that ran out of budget, or all: dense_all)
+        int64_t& nflag = c.nflag;      // the suffix-array run: regions flagged (by the pass that ran out of budget, or all: dense_all)
         if (dense_mode) {
             for (int64_t r = 0; r < nreg; r++) nflag += dense_h[(size_t)r] ? 1 : 0;
             be.h2d(d_dense.p, dense_h.data(), regz);
@@ -415,13 +511,17 @@ public:
         // rows the device derived itself (gaps of the anchor table, rows of the region store) were never seen by the host: the
         // same checks the explicit rows get above, raised through the batch's error word
         if (gb) be.launch("check_rows", (int64_t)nrow, CheckRows{d_R.p, d_starts.p, d_lens.p, ngen, d_glen, d_err});
-        last_alg[0] = last_alg[1] = last_alg[2] = 0;
         if (from_store) {      // the algorithmic bytes of a search whose rows the host never saw (read back with the event counters)
             be.launch_wave("alg_bytes", (nreg * nq + kAlgPairs - 1) / kAlgPairs, AlgBytes{d_R.p, d_lens.p, ngen, nreg * nq, d_alg.p});
         }
+    }
+
+    int build_index(SearchCall& c) {
+        const int64_t nreg = c.nreg, npos = c.npos, nbk = c.nbk, npos_bucketed = c.npos_bucketed, nflag = c.nflag;
+        const size_t regz = c.regz;
+        const RegionInfo* const R = c.R; const std::vector<int64_t>& bbase = c.bbase; uint32_t* const d_err = c.d_err;
         be.mark("index");
-        const size_t kOvfSlot = (size_t)kSlices * kSliceStride + 6, kLostSlot = kOvfSlot + 1;      // (d_counter: overflow records of the bucket build, IndexVerify's count)
-        const uint64_t ovf_cap = nbk > 0 ? (uint64_t)(index_overflow_cap > 0 ? index_overflow_cap : npos_bucketed / 32 + 1024) : 0;
+        const uint64_t ovf_cap = c.ovf_cap = nbk > 0 ? (uint64_t)(index_overflow_cap > 0 ? index_overflow_cap : npos_bucketed / 32 + 1024) : 0;
         if (nbk > 0) {
             // the bucketed regions (index_kernels.h): keys, sorted by bucket, a wavefront per bucket, then the overflow records
             const int pbits = bits_for((uint64_t)npos), bbits = bits_for((uint64_t)nbk);
@@ -437,12 +537,11 @@ public:
             }
             be.launch("index_bucket_bounds", nbk + 1, IndexBucketBounds{d_ikey2.p, npos, pbits, d_bkbegin.p});
             be.launch_wave("index_bucket_fill", nbk, IndexBucketFill{P, d_R.p, nreg, d_bkbase.p, d_ikey2.p, d_bkbegin.p, pbits, d_slots.p, d_filter.p, d_next.p, d_rep.p,
-                                                                     d_counter.p + kOvfSlot, d_ovf.p, ovf_cap});
-            be.launch("index_overflow", (int64_t)ovf_cap, IndexOverflow{P, d_R.p, nreg, d_posbase.p, d_counter.p + kOvfSlot, d_ovf.p, ovf_cap, d_slots.p, d_next.p, d_rep.p});
+                                                                     d_counter.p + kCtrOverflow, d_ovf.p, ovf_cap});
+            be.launch("index_overflow", (int64_t)ovf_cap, IndexOverflow{P, d_R.p, nreg, d_posbase.p, d_counter.p + kCtrOverflow, d_ovf.p, ovf_cap, d_slots.p, d_next.p, d_rep.p});
         }
         if (npos_bucketed < npos) be.launch("index_insert", npos, IndexInsert{P, d_R.p, nreg, d_posbase.p, d_slots.p, d_next.p, d_filter.p, d_rep.p});
-        if (index_verify) be.launch("index_verify", npos, IndexVerify{P, d_R.p, nreg, d_posbase.p, d_slots.p, d_filter.p, d_next.p, d_counter.p + kLostSlot});
-        bool index_counts_read = false;
+        if (index_verify) be.launch("index_verify", npos, IndexVerify{P, d_R.p, nreg, d_posbase.p, d_slots.p, d_filter.p, d_next.p, d_counter.p + kCtrLost});
         be.mark("repeat");
         ensure(d_run, (size_t)std::max<int64_t>(npos, 1));
         be.launch("run_length", npos, RunLength{P, d_R.p, nreg, d_posbase.p, d_run.p});
@@ -451,7 +550,12 @@ public:
             be.mark("dense_sa");
             if (int rc = dense_build(R, nreg, nflag)) return rc;
         }
+        return kNext;
+    }
 
+    int count_units(SearchCall& c) {
+        const int64_t nreg = c.nreg, npairs = c.npairs; const int no_small = c.no_small; const GapBatch* const gb = c.gb;
+        int64_t& nunits = c.nunits; size_t& ev_guess = c.ev_guess; bool& units_known = c.units_known;
         // -- work units (pairs that fit 128 bases on both sides go to SmallPairEvents instead)
         be.mark("units");
         be.launch("count_units", npairs, CountUnits{d_R.p, d_lens.p, ngen, d_ucount.p, g_first, g_last, no_small});
@@ -464,123 +568,137 @@ public:
         if (!gb && nreg == 1) call_ordinal = 0; else if (gb) call_ordinal++;
         const size_t ord = gb || nreg == 1 ? (size_t)call_ordinal : (size_t)-1;      // (-1: a batch of the host route -- it waits for its counts)
         if (ord != (size_t)-1 && call_hints.size() <= ord) call_hints.resize(ord + 1);
-        CallHint none;
-        CallHint& hint = ord != (size_t)-1 ? call_hints[ord] : none;
+        CallHint& hint = *(c.hint = ord != (size_t)-1 ? &call_hints[ord] : &c.none);
         if (hint_shrink > 1) {      // (tests) capacities carried over from the last step, made too small: the repeat paths run
             if (hint.units > 0) hint.units = std::max<int64_t>(1, hint.units / hint_shrink);
             if (hint.ncand > 0) hint.ncand = std::max<int64_t>(1, hint.ncand / hint_shrink);
         }
-        bool units_known = !gb;
+        units_known = !gb;
         if (gb && !(fast_tail && hint.units > 0)) {
             be.d2h(&nunits, d_uoff.p + npairs, 8);
             units_known = true;
         } else if (gb) nunits = hint.units + hint.units / 8 + 64;
         if (nunits >= (1ll << 31)) { error = "too many work units in one batch"; return -5; }
         if (gb) ev_guess += (size_t)nunits * 16;
+        return kNext;
+    }
 
+    // One pass of the event search over the capacities in the record, up to its wait (round trip 1).  kRepeat: a capacity was too
+    // small (the unit count's, an event slice's, a queue's, the grouped events') and has been raised; the pass runs again.
+    int event_pass(SearchCall& c, bool again) {
+        const int64_t nreg = c.nreg, npairs = c.npairs, nbk = c.nbk, nflag = c.nflag; const int lbits = c.lbits, no_small = c.no_small;
+        const bool from_store = c.from_store, first_form = c.first_form, wide_form = c.wide_form, grouping = c.grouping;
+        uint32_t* const d_err = c.d_err; const uint64_t ovf_cap = c.ovf_cap;
+        int64_t &nunits = c.nunits, &nunits_live = c.nunits_live; bool& units_known = c.units_known;
+        size_t &slice_cap = c.slice_cap, &queue_cap = c.queue_cap, &grp_cap = c.grp_cap;
+        std::vector<uint64_t> &counts = c.counts, &qcounts = c.qcounts;
+        uint64_t &nev = c.nev, &nrest = c.nrest, &ngrp = c.ngrp; uint32_t& errbits = c.errbits; bool& index_counts_read = c.index_counts_read;
+        ensure(d_units, (size_t)std::max<int64_t>(nunits, 1));
+        be.launch("fill_units", nunits, FillUnits{P, d_starts.p, d_lens.p, ngen, d_uoff.p, d_ucount.p, npairs, d_units.p});
+        ensure(d_evkey, slice_cap * kSlices); ensure(d_evval, slice_cap * kSlices); ensure(d_rest, queue_cap * kSlices);
+        if (again) be.memset(d_counter.p, 0, 8 * kCtrWords);      // event counters, error word, grouped events
+        if (grouping) {
+            ensure(d_evkey3, grp_cap + ev_cap_hint); ensure(d_evval3, grp_cap + ev_cap_hint);
+            ensure(d_state, grp_cap + ev_cap_hint); ensure(d_emax, grp_cap + ev_cap_hint);
+            be.mark("grouped_events");
+            if (first_form)
+                be.launch_wave("grouped_pair_events", xcd_grid(nreg),
+                               GroupedPairEvents{P, d_R.p, d_starts.p, d_lens.p, ngen, d_rep.p, d_evkey3.p, d_evval3.p, d_counter.p + kCtrGrouped, (uint64_t)grp_cap, lbits,
+                                                 d_glo.p, g_first, g_last, d_gflag.p, d_state.p, d_emax.p, d_epm.p, (int64_t)nreg});
+            if (wide_form)
+                be.launch_wave("grouped_pair_events_wide", xcd_grid(nreg),
+                               GroupedPairEventsWide{P, d_R.p, d_starts.p, d_lens.p, ngen, d_rep.p, d_evkey3.p, d_evval3.p, d_counter.p + kCtrGrouped, (uint64_t)grp_cap, lbits,
+                                                     d_glo.p, g_first, g_last, d_gflag.p, d_state.p, d_emax.p, d_epm.p, (int64_t)nreg, first_form ? 1 : 0, d_counter.p + kCtrWide});
+        }
+        be.memset(d_qcount.p, 0, 8 * (size_t)kSlices * kSliceStride);
+        be.mark("seed_extend");
+        be.launch("seed_extend", nunits * 64,
+                  SeedExtend{P, d_R.p, d_units.p, d_slots.p, d_filter.p, d_next.p, d_rep.p, d_repeated.p,
+                             d_evkey.p, d_evval.p, d_counter.p, (uint64_t)slice_cap, lbits, d_err, work_budget, d_rest.p, d_qcount.p, (uint64_t)queue_cap, d_uoff.p + npairs});
+        if (nunits > 0)      // one lane per queued sample; lanes past a sub-queue's count leave at once (the counts stay on the device)
+            be.launch("seed_rest", (int64_t)(queue_cap * kSlices),
+                      SeedRest{P, d_R.p, d_units.p, d_rest.p, d_qcount.p, (uint64_t)queue_cap, d_slots.p, d_filter.p, d_next.p, d_rep.p,
+                               d_evkey.p, d_evval.p, d_counter.p, (uint64_t)slice_cap, lbits, d_err, work_budget, d_dense.p});
+        if (nunits > 0 && nflag > 0) {      // the probe items of the flagged regions
+            be.mark("dense_search");
+            be.launch("seed_dense", (int64_t)(queue_cap * kSlices),
+                      SeedDense{P, d_R.p, d_units.p, d_rest.p, d_qcount.p, (uint64_t)queue_cap, d_dfi.p, d_dstart.p, d_dval2.p, d_rep.p,
+                                d_evkey.p, d_evval.p, d_counter.p, (uint64_t)slice_cap, lbits});
+            be.mark("seed_extend");
+        }
+        if (!no_small)
+            be.launch("small_pair_events", npairs * 2,
+                      SmallPairEvents{P, d_R.p, d_starts.p, d_lens.p, ngen, d_rep.p, d_evkey.p, d_evval.p, d_counter.p, (uint64_t)slice_cap, lbits, g_first, g_last, grouping ? d_gflag.p : nullptr});
+        be.mark("sort");
+        be.launch_wave("slice_offsets", 1, SliceOffsets{d_counter.p, d_sliceoff.p});
+        group_downloads();      // (the read-backs of this wait: one launch)
+        be.d2h_async(qcounts.data(), d_qcount.p, 8 * qcounts.size());
+        if (from_store) be.d2h_async(alg_sets, d_alg.p, sizeof alg_sets);
+        if (!units_known) be.d2h_async(&nunits_live, d_uoff.p + npairs, 8);
+        run_beside();      // (the caller's host work that needs nothing of this call: the device is busy with the event search)
+        be.d2h(counts.data(), d_counter.p, 8 * counts.size());            // round trip 1: event counts + error word (+ the queues' lengths, + the unit count)
+        if (!index_counts_read) {      // (the first pass of this loop: a repeat clears the counters)
+            index_counts_read = true;
+            if (nbk > 0) last_index_overflow = (int64_t)counts[kCtrOverflow];
+            if (index_verify) last_index_lost = (int64_t)counts[kCtrLost];
+            if (nbk > 0 && counts[kCtrOverflow] > ovf_cap) { index_overflow_seen = (int64_t)counts[kCtrOverflow]; return kIndexRebuild; }
+        }
+        if (!units_known) {
+            units_known = true;
+            if (nunits_live >= (1ll << 31)) { error = "too many work units in one batch"; return -5; }
+            if (nunits_live > nunits) {      // more units than the capacity: the event search again, over all of them
+                nunits = nunits_live;
+                queue_cap = std::max<size_t>(queue_cap, (size_t)nunits * kUnitSamples / 16 / kSlices + 64);
+                tail_repeats++;
+                return kRepeat;
+            }
+        }
+        uint64_t worst = 0, qworst = 0;
+        nev = 0; nrest = 0;
+        for (int sl = 0; sl < kSlices; sl++) {
+            const uint64_t n = counts[(size_t)sl * kSliceStride]; nev += n; worst = std::max(worst, n);
+            const uint64_t q = qcounts[(size_t)sl * kSliceStride]; nrest += q; qworst = std::max(qworst, q);
+        }
+        errbits = (uint32_t)counts[kCtrErr];
+        ngrp = grouping ? counts[kCtrGrouped] : 0;
+        c.worst_slice = worst;      // events of the fullest sub-buffer
+        if (worst <= slice_cap && qworst <= queue_cap && ngrp <= grp_cap) return kNext;
+        if (ngrp > grp_cap) grp_cap = (size_t)(ngrp + ngrp / 8 + 64);
+        if (worst > slice_cap) slice_cap = (size_t)(worst + worst / 8 + 64);
+        if (qworst > queue_cap) queue_cap = (size_t)(qworst + qworst / 8 + 64);
+        c.sticky |= errbits & (kErrWork | kErrRows);      // (RepeatLength's and CheckRows' verdicts: the word is cleared with the counters)
+        return kRepeat;
+    }
+
+    int search_events(SearchCall& c) {
+        const int64_t nreg = c.nreg, npairs = c.npairs, nunits = c.nunits; const int nq = c.nq, no_small = c.no_small;
         // -- events: kSlices append buffers (retry with larger ones on overflow), gathered, then sorted by (pair, l, strand)
         ensure(d_sliceoff, (size_t)kSlices + 1);
-        uint64_t nev = 0;
-        size_t slice_cap = (std::min<size_t>(std::max<size_t>(ev_cap_hint, ev_guess), (size_t)1 << 31) + kSlices - 1) / kSlices + 64;
-        std::vector<uint64_t> counts(ncounter);
-        uint32_t errbits = 0;
+        c.slice_cap = (std::min<size_t>(std::max<size_t>(ev_cap_hint, c.ev_guess), (size_t)1 << 31) + kSlices - 1) / kSlices + 64;
+        c.counts.assign(kCtrWords, 0);
         // samples that SeedExtend hands to SeedRest: kSlices sub-queues sized from what earlier calls needed (first guess: one
         // sample in sixteen), repeated with the exact size if one overflows (the counters keep counting past the capacity)
         ensure(d_qcount, (size_t)kSlices * kSliceStride);
-        size_t queue_cap = std::max<size_t>(std::max<size_t>(rest_cap_hint[nreg == 1], (size_t)nunits * kUnitSamples / 16 / kSlices), 64) + 64;      // (anchor-shaped and recursion-shaped calls alternate)
-        uint64_t nrest = 0;
-        uint32_t sticky = 0;
-        std::vector<uint64_t> qcounts((size_t)kSlices * kSliceStride);
+        c.queue_cap = std::max<size_t>(std::max<size_t>(rest_cap_hint[nreg == 1], (size_t)nunits * kUnitSamples / 16 / kSlices), 64) + 64;      // (anchor-shaped and recursion-shaped calls alternate)
+        c.qcounts.assign((size_t)kSlices * kSliceStride, 0);
         // the small regions of a recursion batch: their events once per distinct piece, straight into the head of the final array
         // (the first form up to kGrpGenomes query genomes; the wide form after it over the regions it left, or alone up to kWideGenomes)
-        const bool small_groups = group_small && !no_small && !want_events && nreg >= 2;
-        const bool first_form = small_groups && nq <= kGrpGenomes;
-        const bool wide_form = small_groups && group_wide && nq <= kWideGenomes;
-        const bool grouping = first_form || wide_form;
-        const size_t kGrpSlot = (size_t)kSlices * kSliceStride + 2;      // (d_counter: the block counter of the grouped events)
-        const size_t kWideSlot = kGrpSlot + 1;                           // (... and the wide form's counts: events, regions handed back, regions taken)
-        size_t grp_cap = grouping ? std::max<size_t>(grp_cap_hint, (size_t)npairs * 3) + 64 : 0;
-        uint64_t ngrp = 0;
+        const bool small_groups = group_small && !no_small && !c.want_events && nreg >= 2;
+        const bool first_form = c.first_form = small_groups && nq <= kGrpGenomes;
+        const bool wide_form = c.wide_form = small_groups && group_wide && nq <= kWideGenomes;
+        const bool grouping = c.grouping = first_form || wide_form;
+        c.grp_cap = grouping ? std::max<size_t>(grp_cap_hint, (size_t)npairs * 3) + 64 : 0;
         if (grouping) { ensure(d_gflag, (size_t)nreg); ensure(d_glo, (size_t)npairs); }
-        int64_t nunits_live = nunits;
-        uint64_t worst_slice = 0;      // events of the fullest sub-buffer
-        for (bool again = false;; again = true) {
-            ensure(d_units, (size_t)std::max<int64_t>(nunits, 1));
-            be.launch("fill_units", nunits, FillUnits{P, d_starts.p, d_lens.p, ngen, d_uoff.p, d_ucount.p, npairs, d_units.p});
-            ensure(d_evkey, slice_cap * kSlices); ensure(d_evval, slice_cap * kSlices); ensure(d_rest, queue_cap * kSlices);
-            if (again) be.memset(d_counter.p, 0, 8 * ncounter);      // event counters, error word, grouped events
-            if (grouping) {
-                ensure(d_evkey3, grp_cap + ev_cap_hint); ensure(d_evval3, grp_cap + ev_cap_hint);
-                ensure(d_state, grp_cap + ev_cap_hint); ensure(d_emax, grp_cap + ev_cap_hint);
-                be.mark("grouped_events");
-                if (first_form)
-                    be.launch_wave("grouped_pair_events", xcd_grid(nreg),
-                                   GroupedPairEvents{P, d_R.p, d_starts.p, d_lens.p, ngen, d_rep.p, d_evkey3.p, d_evval3.p, d_counter.p + kGrpSlot, (uint64_t)grp_cap, lbits,
-                                                     d_glo.p, g_first, g_last, d_gflag.p, d_state.p, d_emax.p, d_epm.p, (int64_t)nreg});
-                if (wide_form)
-                    be.launch_wave("grouped_pair_events_wide", xcd_grid(nreg),
-                                   GroupedPairEventsWide{P, d_R.p, d_starts.p, d_lens.p, ngen, d_rep.p, d_evkey3.p, d_evval3.p, d_counter.p + kGrpSlot, (uint64_t)grp_cap, lbits,
-                                                         d_glo.p, g_first, g_last, d_gflag.p, d_state.p, d_emax.p, d_epm.p, (int64_t)nreg, first_form ? 1 : 0, d_counter.p + kWideSlot});
-            }
-            be.memset(d_qcount.p, 0, 8 * (size_t)kSlices * kSliceStride);
-            be.mark("seed_extend");
-            be.launch("seed_extend", nunits * 64,
-                      SeedExtend{P, d_R.p, d_units.p, d_slots.p, d_filter.p, d_next.p, d_rep.p, d_repeated.p,
-                                 d_evkey.p, d_evval.p, d_counter.p, (uint64_t)slice_cap, lbits, d_err, work_budget, d_rest.p, d_qcount.p, (uint64_t)queue_cap, d_uoff.p + npairs});
-            if (nunits > 0)      // one lane per queued sample; lanes past a sub-queue's count leave at once (the counts stay on the device)
-                be.launch("seed_rest", (int64_t)(queue_cap * kSlices),
-                          SeedRest{P, d_R.p, d_units.p, d_rest.p, d_qcount.p, (uint64_t)queue_cap, d_slots.p, d_filter.p, d_next.p, d_rep.p,
-                                   d_evkey.p, d_evval.p, d_counter.p, (uint64_t)slice_cap, lbits, d_err, work_budget, d_dense.p});
-            if (nunits > 0 && nflag > 0) {      // the probe items of the flagged regions
-                be.mark("dense_search");
-                be.launch("seed_dense", (int64_t)(queue_cap * kSlices),
-                          SeedDense{P, d_R.p, d_units.p, d_rest.p, d_qcount.p, (uint64_t)queue_cap, d_dfi.p, d_dstart.p, d_dval2.p, d_rep.p,
-                                    d_evkey.p, d_evval.p, d_counter.p, (uint64_t)slice_cap, lbits});
-                be.mark("seed_extend");
-            }
-            if (!no_small)
-                be.launch("small_pair_events", npairs * 2,
-                          SmallPairEvents{P, d_R.p, d_starts.p, d_lens.p, ngen, d_rep.p, d_evkey.p, d_evval.p, d_counter.p, (uint64_t)slice_cap, lbits, g_first, g_last, grouping ? d_gflag.p : nullptr});
-            be.mark("sort");
-            be.launch_wave("slice_offsets", 1, SliceOffsets{d_counter.p, d_sliceoff.p});
-            group_downloads();      // (the read-backs of this wait: one launch)
-            be.d2h_async(qcounts.data(), d_qcount.p, 8 * qcounts.size());
-            if (from_store) be.d2h_async(alg_sets, d_alg.p, sizeof alg_sets);
-            if (!units_known) be.d2h_async(&nunits_live, d_uoff.p + npairs, 8);
-            run_beside();      // (the caller's host work that needs nothing of this call: the device is busy with the event search)
-            be.d2h(counts.data(), d_counter.p, 8 * counts.size());            // round trip 1: event counts + error word (+ the queues' lengths, + the unit count)
-            if (!index_counts_read) {      // (the first pass of this loop: a repeat clears the counters)
-                index_counts_read = true;
-                if (nbk > 0) last_index_overflow = (int64_t)counts[kOvfSlot];
-                if (index_verify) last_index_lost = (int64_t)counts[kLostSlot];
-                if (nbk > 0 && counts[kOvfSlot] > ovf_cap) { index_overflow_seen = (int64_t)counts[kOvfSlot]; return kIndexRebuild; }
-            }
-            if (!units_known) {
-                units_known = true;
-                if (nunits_live >= (1ll << 31)) { error = "too many work units in one batch"; return -5; }
-                if (nunits_live > nunits) {      // more units than the capacity: the event search again, over all of them
-                    nunits = nunits_live;
-                    queue_cap = std::max<size_t>(queue_cap, (size_t)nunits * kUnitSamples / 16 / kSlices + 64);
-                    tail_repeats++;
-                    continue;
-                }
-            }
-            uint64_t worst = 0, qworst = 0;
-            nev = 0; nrest = 0;
-            for (int sl = 0; sl < kSlices; sl++) {
-                const uint64_t c = counts[(size_t)sl * kSliceStride]; nev += c; worst = std::max(worst, c);
-                const uint64_t q = qcounts[(size_t)sl * kSliceStride]; nrest += q; qworst = std::max(qworst, q);
-            }
-            errbits = (uint32_t)counts[(size_t)kSlices * kSliceStride];
-            ngrp = grouping ? counts[kGrpSlot] : 0;
-            worst_slice = worst;
-            if (worst <= slice_cap && qworst <= queue_cap && ngrp <= grp_cap) break;
-            if (ngrp > grp_cap) grp_cap = (size_t)(ngrp + ngrp / 8 + 64);
-            if (worst > slice_cap) slice_cap = (size_t)(worst + worst / 8 + 64);
-            if (qworst > queue_cap) queue_cap = (size_t)(qworst + qworst / 8 + 64);
-            sticky |= errbits & (kErrWork | kErrRows);      // (RepeatLength's and CheckRows' verdicts: the word is cleared with the counters)
-        }
-        errbits |= sticky;
+        c.nunits_live = nunits;
+        int rc;
+        for (bool again = false; (rc = event_pass(c, again)) == kRepeat; again = true) {}
+        if (rc != kNext) return rc;
+
+        const GapBatch* const gb = c.gb; const bool from_store = c.from_store; CallHint& hint = *c.hint;
+        const std::vector<uint64_t>& counts = c.counts;
+        const uint64_t nev = c.nev, nrest = c.nrest, ngrp = c.ngrp; const size_t queue_cap = c.queue_cap; const int64_t nunits_live = c.nunits_live;
+        uint32_t& errbits = c.errbits;
+        errbits |= c.sticky;
         if (from_store) {
             alg_raw[0] = alg_raw[1] = alg_raw[2] = 0;
             for (int x = 0; x < kAlgSets; x++) for (int k = 0; k < 3; k++) alg_raw[k] += alg_sets[8 * x + k];
@@ -594,23 +712,29 @@ public:
         if (grouping) grp_cap_hint = (size_t)(ngrp + ngrp / 4);
         last_events = (int64_t)(nev + ngrp);
         last_grouped = (int64_t)ngrp;
-        last_grouped_wide = wide_form ? (int64_t)counts[kWideSlot] : 0;
-        last_handed_back = wide_form ? (int64_t)counts[kWideSlot + 1] : -1;      // (-1: nobody counted them -- the wide form did not run)
-        last_wide_regions = wide_form ? (int64_t)counts[kWideSlot + 2] : 0;
+        last_grouped_wide = wide_form ? (int64_t)counts[kCtrWide] : 0;
+        last_handed_back = wide_form ? (int64_t)counts[kCtrWide + 1] : -1;      // (-1: nobody counted them -- the wide form did not run)
+        last_wide_regions = wide_form ? (int64_t)counts[kCtrWide + 2] : 0;
         // a rank of a sharded run that ran out of budget must not leave the others waiting in the collectives: the
         // verdict travels with the first exchange (below) and every rank returns the error together
-        const bool sharded = coll.world > 1 || coll.device;      // (a one-rank RCCL session still runs the exchanges: that is how a 1-GPU box tests them)
+        const bool sharded = c.sharded = coll.world > 1 || coll.device;      // (a one-rank RCCL session still runs the exchanges: that is how a 1-GPU box tests them)
         if ((errbits & kErrWork) && !sharded) { budget_exceeded = true; error = "per-thread work budget exceeded (degenerate repeat structure in a region)"; return -5; }
+        return kNext;
+    }
 
+    void order_events(SearchCall& c) {
+        const int64_t nreg = c.nreg, npairs = c.npairs, npos = c.npos, nchunks = c.nchunks, centries = c.centries; const int nq = c.nq, lbits = c.lbits;
+        const uint64_t ngrp = c.ngrp, worst_slice = c.worst_slice; const size_t slice_cap = c.slice_cap; const bool grouping = c.grouping;
+        uint64_t& nev = c.nev;
         ensure(d_evkey2, std::max<size_t>(nev, 1)); ensure(d_evval2, std::max<size_t>(nev, 1));
         // the final array: [ grouped events, contiguous and ordered per pair | the other events, sorted by (pair, l, strand) ]
         ensure_keep(d_evkey3, std::max<size_t>(ngrp + nev, 1), (size_t)ngrp); ensure_keep(d_evval3, std::max<size_t>(ngrp + nev, 1), (size_t)ngrp);
         const int keybits = bits_for((uint64_t)npairs) + lbits + 1;
-        uint64_t *skey = d_evkey3.p, *sval = d_evval3.p;
+        uint64_t *skey = c.skey = d_evkey3.p, *sval = c.sval = d_evval3.p;
         // the events in order: by buckets (pair, 256-position block) whose scanned counts are the readers' coarse table as well, or
         // (tune bucket_sort = 0: rounds 1-5) gathered, radix-sorted, and the table from a pass over the sorted keys
         const int64_t nbuckets = (int64_t)nq * nchunks;
-        const bool by_buckets = bucket_sort && nev > 0 && nbuckets < ((int64_t)1 << 31);
+        const bool by_buckets = c.by_buckets = bucket_sort && nev > 0 && nbuckets < ((int64_t)1 << 31);
         ensure(d_lo, (size_t)npairs + 1);
         if (by_buckets) {
             ensure(d_bcount, (size_t)nbuckets + 1); ensure(d_bbegin, (size_t)nbuckets + 1); ensure(d_pbase, (size_t)npairs);
@@ -644,39 +768,51 @@ public:
             be.launch_wave("wave_scan", nwaves, WaveScan{core, d_wsummary.p, d_lo.p, (int64_t)ngrp, d_state.p + ngrp, d_emax.p + ngrp});
         }
 
-        if (want_events) {   // parity hook (pm_find_events): sorted events + rep'
+        if (c.want_events) {   // parity hook (pm_find_events): sorted events + rep'
             ev_key_h.resize((size_t)nev); ev_val_h.resize((size_t)nev); rep_h.resize((size_t)npos);
             if (nev) { be.d2h(ev_key_h.data(), skey, 8 * (size_t)nev); be.d2h(ev_val_h.data(), sval, 8 * (size_t)nev); }
             if (npos) be.d2h(rep_h.data(), d_rep.p, 4 * (size_t)npos);
             ev_lbits = lbits;
         }
+    }
 
-        if (mumi) {
-            be.mark("mumi_coverage");
-            ensure(d_cov, (size_t)npairs);
-            be.launch("mumi_coverage", npairs, MumiCoverage{d_R.p, skey, sval, d_lo.p, d_state.p, d_rep.p, lbits, ngen, d_cov.p});
-            mumi_covered.resize((size_t)npairs);
-            be.d2h(mumi_covered.data(), d_cov.p, 8 * (size_t)npairs);
-            if (sharded) {   // every rank computed its own genome block: gather the blocks (+ the ranks' error words)
-                int widest = 0;
-                for (int r = 0; r < coll.world; r++) { int a, b; shard_range(ngen, r, coll.world, &a, &b); widest = std::max(widest, b - a); }
-                const size_t per = (size_t)std::max(widest, 1) + 1;
-                std::vector<int64_t> send(per, 0), recv(per * (size_t)coll.world);
-                for (int g = g_first; g < g_last; g++) send[(size_t)(g - g_first)] = mumi_covered[(size_t)(g - 1)];
-                send[per - 1] = errbits;
-                if (allgather_host(send.data(), (int64_t)(8 * send.size()), recv.data())) { error = "all-gather of MUMi coverage failed"; return -4; }
-                for (int r = 0; r < coll.world; r++) {
-                    int a, b; shard_range(ngen, r, coll.world, &a, &b);
-                    for (int g = a; g < b; g++) mumi_covered[(size_t)(g - 1)] = recv[(size_t)r * per + (size_t)(g - a)];
-                    errbits |= (uint32_t)recv[(size_t)r * per + per - 1];
-                }
-                if (errbits & kErrWork) { budget_exceeded = true; error = "per-thread work budget exceeded on some rank (degenerate repeat structure in a region)"; return -5; }
+    // the widest genome block of a sharded run (one genome at least): what every rank's block is padded to in an exchange
+    int widest_block() const {
+        int widest = 0;
+        for (int r = 0; r < coll.world; r++) { int a, b; shard_range(ngen, r, coll.world, &a, &b); widest = std::max(widest, b - a); }
+        return std::max(widest, 1);
+    }
+
+    int mumi_tail(SearchCall& c) {
+        const int64_t npairs = c.npairs; const int lbits = c.lbits; const bool sharded = c.sharded;
+        uint64_t* const skey = c.skey; uint64_t* const sval = c.sval; uint32_t& errbits = c.errbits;
+        be.mark("mumi_coverage");
+        ensure(d_cov, (size_t)npairs);
+        be.launch("mumi_coverage", npairs, MumiCoverage{d_R.p, skey, sval, d_lo.p, d_state.p, d_rep.p, lbits, ngen, d_cov.p});
+        mumi_covered.resize((size_t)npairs);
+        be.d2h(mumi_covered.data(), d_cov.p, 8 * (size_t)npairs);
+        if (sharded) {   // every rank computed its own genome block: gather the blocks (+ the ranks' error words)
+            const size_t per = (size_t)widest_block() + 1;
+            std::vector<int64_t> send(per, 0), recv(per * (size_t)coll.world);
+            for (int g = g_first; g < g_last; g++) send[(size_t)(g - g_first)] = mumi_covered[(size_t)(g - 1)];
+            send[per - 1] = errbits;
+            if (allgather_host(send.data(), (int64_t)(8 * send.size()), recv.data())) { error = "all-gather of MUMi coverage failed"; return -4; }
+            for (int r = 0; r < coll.world; r++) {
+                int a, b; shard_range(ngen, r, coll.world, &a, &b);
+                for (int g = a; g < b; g++) mumi_covered[(size_t)(g - 1)] = recv[(size_t)r * per + (size_t)(g - a)];
+                errbits |= (uint32_t)recv[(size_t)r * per + per - 1];
             }
-            be.mark(nullptr);
-            collect_timing();
-            return 0;
+            if (errbits & kErrWork) { budget_exceeded = true; error = "per-thread work budget exceeded on some rank (degenerate repeat structure in a region)"; return -5; }
         }
+        be.mark(nullptr);
+        collect_timing();
+        return 0;
+    }
 
+    int master_ep(SearchCall& c) {
+        const int64_t nreg = c.nreg, npos = c.npos, nchunks = c.nchunks, nwv = c.nwv; const int nq = c.nq, lbits = c.lbits;
+        const uint64_t nev = c.nev, ngrp = c.ngrp; const uint32_t errbits = c.errbits; const bool by_buckets = c.by_buckets, grouping = c.grouping, sharded = c.sharded;
+        uint64_t* const skey = c.skey; int32_t& verdict = c.verdict;
         // -- Master.EP, candidates
         be.mark("master_ep");
         // (by buckets: the table came with the order -- but for the grouped regions' pairs, whose events never were in a bucket)
@@ -684,7 +820,6 @@ public:
         else if (ngrp > 0) be.launch("coarse_fill", (int64_t)ngrp, CoarseFill{skey, (int64_t)ngrp, lbits, d_lo.p, d_R.p, d_cbase.p, nq, d_coarse.p});
         if (master_seg) be.launch_wave("master_ep_seg", xcd_grid(nchunks), MasterEPSeg{d_R.p, nreg, ngen, skey, d_lo.p, d_emax.p, lbits, d_epm.p, d_cbase.p, d_coarse.p, g_first, g_last, grouping ? d_gflag.p : nullptr, nchunks});
         else be.launch_wave("master_ep", xcd_grid(nchunks), MasterEP{d_R.p, nreg, ngen, skey, d_lo.p, d_emax.p, lbits, d_epm.p, d_cbase.p, d_coarse.p, g_first, g_last, grouping ? d_gflag.p : nullptr, nchunks});
-        int32_t verdict = 0;
         if (sharded && coll.device) {   // exchange 1 on the device: RCCL all-reduce(min) of Master.EP in place, + the error verdict word
             be.mark("exchange_ep");
             be.fill32(d_epm.p + npos, (errbits & kErrWork) ? -1 : 0);
@@ -702,188 +837,225 @@ public:
         be.mark("candidates");
         be.launch_wave("cand_mark", nwv, CandMark{d_R.p, nreg, d_posbase.p, npos, d_epm.p, d_wmask.p, d_wcount.p});
         be.exclusive_scan(d_wcount.p, d_woff.p, (size_t)nwv + 1);
-        const int64_t* ncand_p = d_woff.p + nwv;      // the candidate count, where the device keeps it
+        c.ncand_p = d_woff.p + nwv;      // the candidate count, where the device keeps it
+        return kNext;
+    }
+
+    int candidate_tail(SearchCall& c) {
+        const int64_t nreg = c.nreg; const GapBatch* const gb = c.gb; const bool from_store = c.from_store, sharded = c.sharded; const CallHint& hint = *c.hint;
         // The rest of the call -- candidates listed, folded over the genomes, the accepted ones compacted into rows, the overlap flags
         // of a long list -- used to wait twice for the device, for the candidate count and for the accepted count, because the
         // launches and buffers were sized with them.  A call whose rows stay on the device (the resident route's anchor call and its
         // store searches) no longer does: launches and buffers take CAPACITIES from what the last call of the same shape needed,
         // every kernel reads the live count from device memory, and both counts come back with the results, in the call's one last
         // wait.  A capacity that turns out too small (or an anchor list that turns out short) repeats the tail the exact way.
-        const bool anchor_guess = nreg == 1 && !gb && hint.nok >= dirty_min;
+        const bool anchor_guess = c.anchor_guess = nreg == 1 && !gb && hint.nok >= dirty_min;
         const bool may_skip_waits = !sharded && want_rows && resident && hint.ncand > 0 && (from_store || anchor_guess) && fast_tail;
-        for (int attempt = may_skip_waits ? 0 : 1;; attempt++) {
-            const bool exact = attempt > 0;
-            int64_t ncand_i = 0;
-            if (exact) be.d2h(&ncand_i, ncand_p, 8);                                   // round trip 2: candidate count
-            if (verdict < 0) { budget_exceeded = true; error = "per-thread work budget exceeded on some rank (degenerate repeat structure in a region)"; return -5; }
-            if (exact) {
-                last_candidates = ncand_i;
-                if (ncand_i == 0) { hint.ncand = 1; hint.nok = 0; if (resident && from_store) out->store_base = ms_count; be.mark(nullptr); collect_timing(); return 0; }
-            }
-            // capacity of the candidate list: the count itself when it is known
-            const uint64_t ncand = exact ? (uint64_t)ncand_i : (uint64_t)(hint.ncand + hint.ncand / 8 + 256);
-            ensure(d_cand, (size_t)ncand);
-            be.launch("cand_write", nwv * 64, CandWrite{d_R.p, nreg, d_posbase.p, d_wmask.p, d_woff.p, d_cand.p, ncand});
-            const uint64_t* scand = d_cand.p;        // in (region, k) order by construction
-
-            // -- per-candidate genome fold
-            be.mark("fold");
-            ensure(d_ok, (size_t)ncand); ensure(d_ok_k, (size_t)ncand); ensure(d_ok_lon, (size_t)ncand);
-            ensure(d_osp, (size_t)ncand * (size_t)nq); ensure(d_ofwd, (size_t)ncand * (size_t)nq);
-            const GenomeAtK* at = nullptr;
-            if (sharded) {   // exchange 2: every rank contributes the (EP,UP,SP) columns of its genome block
-                ensure(d_at, (size_t)ncand * (size_t)nq);
-                be.launch("state_at_candidate", (int64_t)ncand * nq, StateAtCandidate{d_R.p, scand, ngen, skey, sval, d_lo.p, d_state.p, d_rep.p, lbits, d_at.p, d_cbase.p, d_coarse.p});
-                be.mark("exchange_states");
-                const size_t nqz = (size_t)nq, cz = (size_t)ncand;
-                int widest = 0;
-                for (int r = 0; r < coll.world; r++) { int a, b; shard_range(ngen, r, coll.world, &a, &b); widest = std::max(widest, b - a); }
-                widest = std::max(widest, 1);
-                const size_t blk = cz * (size_t)widest;
-                if (coll.device) {      // pack this rank's columns, RCCL all-gather on the engine's stream, spread the blocks: nothing leaves the device
-                    ensure(d_xsend, blk); ensure(d_xrecv, blk * (size_t)coll.world);
-                    be.launch("pack_states", (int64_t)blk, PackStates{d_at.p, nq, g_first - 1, g_last - g_first, widest, d_xsend.p});
-                    if (be.allgather_dev(d_xsend.p, (int64_t)(sizeof(GenomeAtK) * blk), d_xrecv.p)) { error = "RCCL all-gather of candidate states failed: " + be.error(); return -4; }
-                    be.launch("unpack_states", (int64_t)(cz * nqz), UnpackStates{d_xrecv.p, nq, coll.world, widest, (int64_t)ncand, d_at.p});
-                } else {
-                    std::vector<GenomeAtK> all(cz * nqz);
-                    be.d2h(all.data(), d_at.p, sizeof(GenomeAtK) * all.size());
-                    std::vector<GenomeAtK> send(blk), recv(blk * (size_t)coll.world);
-                    const size_t mine = (size_t)(g_last - g_first);
-                    for (size_t c = 0; c < cz; c++)
-                        for (size_t x = 0; x < mine; x++) send[c * (size_t)widest + x] = all[c * nqz + (size_t)(g_first - 1) + x];
-                    if (coll.allgather(coll.ctx, send.data(), (int64_t)(sizeof(GenomeAtK) * send.size()), recv.data())) { error = "all-gather of candidate states failed"; return -4; }
-                    for (int r = 0; r < coll.world; r++) {
-                        int a, b; shard_range(ngen, r, coll.world, &a, &b);
-                        const GenomeAtK* src = recv.data() + (size_t)r * send.size();
-                        for (size_t c = 0; c < cz; c++)
-                            for (int x = 0; x < b - a; x++) all[c * nqz + (size_t)(a - 1 + x)] = src[c * (size_t)widest + (size_t)x];
-                    }
-                    be.h2d(d_at.p, all.data(), sizeof(GenomeAtK) * all.size());
-                }
-                be.mark("fold");
-                at = d_at.p;
-            }
-            be.launch_wave("fold_candidates", xcd_grid((int64_t)ncand),
-                           FoldCandidates{d_R.p, scand, ngen, at, skey, sval, d_lo.p, d_state.p, d_rep.p, lbits, d_cbase.p, d_coarse.p,
-                                          d_ok_k.p, d_ok_lon.p, d_osp.p, d_ofwd.p, d_ok.p, (int64_t)ncand, ncand_p});
-
-            // -- accepted candidates, compacted on the device and downloaded straight into the result's blocks
-            be.mark("compact");
-            ensure(d_okcnt, (size_t)ncand + 1); ensure(d_okpos, (size_t)ncand + 1);
-            be.launch("ok_count", (int64_t)ncand + 1, OkCount{d_ok.p, ncand_p, d_okcnt.p, (int64_t)ncand});
-            be.exclusive_scan(d_okcnt.p, d_okpos.p, (size_t)ncand + 1);
-            const int64_t* nok_p = d_okpos.p + ncand;      // the accepted count, where the device keeps it
-            int64_t nok = 0;
-            if (exact) be.d2h(&nok, nok_p, 8);                                    // round trip 3: accepted count
-            // capacity of the accepted rows: the count itself when it is known, else every candidate could be accepted
-            const size_t nokz = exact ? (size_t)nok : (size_t)ncand, nqz2 = (size_t)nq, ngz = (size_t)ngen;
-            ensure(d_creg, std::max<size_t>(nokz, 1)); ensure(d_ck, std::max<size_t>(nokz, 1)); ensure(d_clon, std::max<size_t>(nokz, 1));
-            std::vector<int32_t> reg_h(nokz);
-            out->release();
-            out->kb = pool->take(4 * nokz); out->lonb = pool->take(4 * nokz);
-            out->rows = want_rows; out->dirty_known = false; out->table_id = 0; out->store_base = -1;
-            const int64_t ms_before = ms_count, rg_before = rg_count, lay_before = layout_rows, pkey_before = rg_pkey_init;
-            bool anchor_call = false;
-            if (!want_rows) {
-                ensure(d_csp, std::max<size_t>(nokz * nqz2, 1)); ensure(d_cfwd, std::max<size_t>(nokz * nqz2, 1));
-                be.launch("compact_sp", (int64_t)ncand * nq,
-                          CompactSp{scand, d_ok.p, d_okpos.p, nq, d_ok_k.p, d_ok_lon.p, d_osp.p, d_ofwd.p, d_creg.p, d_ck.p, d_clon.p, d_csp.p, d_cfwd.p, ncand_p});
-                be.mark("download");
-                group_downloads();
-                out->spb = pool->take(4 * nokz * nqz2); out->fwdb = pool->take(nokz * nqz2);
-                be.d2h_async(out->spb.p, d_csp.p, 4 * nokz * nqz2);
-                be.d2h_async(out->fwdb.p, d_cfwd.p, nokz * nqz2);
-            } else {
-                // Resident mode (pm_session_rows(s, 2)): the rows of the anchor call, and of every search of regions of the region store,
-                // stay on the device as rows of the MUM store -- the host receives the per-row scalars only (flags, k, length).  The
-                // anchor call's rows are the session's anchor table (= rows [0, A) of the store) in either mode.  The compaction
-                // writes such rows straight into the store (a copy of the 60 MB anchor table is half a millisecond).
-                anchor_call = nreg == 1 && !gb && (exact ? nok >= dirty_min : anchor_guess);
-                const bool keep_rows = resident && (anchor_call || from_store);
-                const bool to_store = anchor_call || keep_rows;
-                int32_t* p_start; uint8_t* p_strand; int32_t* p_lon; uint32_t* p_flags;
-                if (to_store) {
-                    if (anchor_call) { ms_count = 0; rg_count = 0; layout_rows = -1; rg_pkey_init = 0; }      // (a new region store: none of its regions has been processed)
-                    const size_t base = (size_t)ms_count, upto = base + nokz;
-                    ensure_keep(d_anchor_start, std::max<size_t>(upto * ngz, 1), base * ngz); ensure_keep(d_ms_strand, std::max<size_t>(upto * ngz, 1), base * ngz);
-                    ensure_keep(d_anchor_lon, std::max<size_t>(upto, 1), base); ensure_keep(d_anchor_flags, std::max<size_t>(upto, 1), base);
-                    ensure_keep(d_ms_shift, std::max<size_t>(upto, 1), base); ensure_keep(d_ms_len, std::max<size_t>(upto, 1), base); ensure_keep(d_ms_state, std::max<size_t>(upto, 1), base);
-                    p_start = d_anchor_start.p + base * ngz; p_strand = d_ms_strand.p + base * ngz; p_lon = d_anchor_lon.p + base; p_flags = d_anchor_flags.p + base;
-                    out->store_base = (int64_t)base;
-                    ms_count = (int64_t)upto;      // (capacity: set to base + the accepted count once that is known)
-                } else {
-                    ensure(d_csp, std::max<size_t>(nokz * ngz, 1)); ensure(d_cfwd, std::max<size_t>(nokz * ngz, 1)); ensure(d_cflags, std::max<size_t>(nokz, 1));
-                    p_start = d_csp.p; p_strand = d_cfwd.p; p_lon = d_clon.p; p_flags = d_cflags.p;
-                }
-                const bool long_list = nreg == 1 && (exact ? nok >= dirty_min : anchor_guess);
-                if (long_list) ensure(d_dirty, nokz);
-                {      // the flags of the rows (OR-ed into), the cheap overlap test's marks, shift and state of the new store rows: one launch
-                    const ClearJob jobs[] = {{p_flags, 4 * nokz, 0}, {long_list ? d_dirty.p : nullptr, long_list ? 4 * nokz : 0, 0},
-                                             {to_store ? d_ms_shift.p + (ms_count - (int64_t)nokz) : nullptr, to_store ? 4 * nokz : 0, 0},
-                                             {to_store ? d_ms_state.p + (ms_count - (int64_t)nokz) : nullptr, to_store ? nokz : 0, 0}};
-                    be.clear_many(jobs, 4);
-                }
-                be.launch("compact_candidates", (int64_t)ncand * ngen,
-                          CompactCandidates{scand, d_ok.p, d_okpos.p, ngen, d_ok_k.p, d_ok_lon.p, d_osp.p, d_ofwd.p, d_starts.p, d_lens.p, d_glen,
-                                            d_creg.p, d_ck.p, p_lon, p_start, p_strand, p_flags, ncand_p});
-                if (long_list) {     // a long list of one region (the anchor call): the cheap overlap test on the device
-                    const int64_t nblocks = ((int64_t)nokz + kDirtyBlock - 1) / kDirtyBlock, groups = (ngen + 63) / 64;
-                    ensure(d_bmax, (size_t)nblocks * ngz); ensure(d_bmin, (size_t)nblocks * ngz);
-                    be.launch_wave("dirty_extent", nblocks * groups, DirtyExtent{p_start, p_lon, p_flags, nok_p, ngen, d_bmax.p, d_bmin.p});
-                    be.launch_wave("dirty_prefix", groups, DirtyPrefix{nblocks, ngen, d_bmax.p, d_bmin.p});
-                    be.launch_wave("dirty_mark", nblocks * groups, DirtyMark{p_start, p_lon, nok_p, ngen, d_bmax.p, d_bmin.p, p_flags, d_dirty.p});
-                    be.launch("dirty_merge", (int64_t)nokz, DirtyMerge{d_dirty.p, p_flags, nok_p});
-                    out->dirty_known = true;
-                }
-                if (to_store) {
-                    be.d2d(d_ms_len.p + (ms_count - (int64_t)nokz), p_lon, 4 * nokz);
-                    if (anchor_call) out->table_id = ++table_counter;
-                }
-                be.mark("download");
-                group_downloads();      // (flags, lengths, regions, k and the two counts: one launch instead of seven copies)
-                out->flagsb = pool->take(4 * nokz);
-                be.d2h_async(out->flagsb.p, p_flags, 4 * nokz);
-                if (!keep_rows) {
-                    out->startb = pool->take(4 * nokz * ngz); out->strandb = pool->take(nokz * ngz);
-                    be.d2h_async(out->startb.p, p_start, 4 * nokz * ngz);
-                    be.d2h_async(out->strandb.p, p_strand, nokz * ngz);
-                }
-                be.d2h_async(out->lonb.p, p_lon, 4 * nokz);
-            }
-            if (!want_rows) be.d2h_async(out->lonb.p, d_clon.p, 4 * nokz);
-            be.d2h_async(reg_h.data(), d_creg.p, 4 * nokz);
-            be.d2h_async(out->kb.p, d_ck.p, 4 * nokz);
-            int64_t counts_h[2] = {ncand_i, nok};
-            if (!exact) { be.d2h_async(&counts_h[0], ncand_p, 8); be.d2h_async(&counts_h[1], nok_p, 8); }
-            flush_downloads();
-            be.mark(nullptr);
-            be.sync();                                                         // round trip 4: the results (and, where the call did not wait for them, the two counts)
-            if (!exact) {
-                ncand_i = counts_h[0]; nok = counts_h[1];
-                const bool fits = (uint64_t)ncand_i <= ncand && anchor_call == (nreg == 1 && !gb && nok >= dirty_min);
-                if (!fits) {      // the capacity was too small, or the list is not the long list it was taken for: again, with the counts
-                    ms_count = ms_before; rg_count = rg_before; layout_rows = lay_before; rg_pkey_init = pkey_before;
-                    tail_repeats++;
-                    be.mark("candidates");
-                    continue;
-                }
-                last_candidates = ncand_i;
-                if (out->store_base >= 0) ms_count = out->store_base + nok;
-            }
-            hint.ncand = std::max<int64_t>(ncand_i, 1); hint.nok = nok;
-            last_accepted = nok;
-            if (anchor_call) { anchor_table_rows = nok; anchor_table_id = out->table_id; }
-            for (int64_t w = 0; w < nok; w++) out->off[(size_t)reg_h[(size_t)w] + 1]++;
-            for (int64_t r = 0; r < nreg; r++) out->off[(size_t)r + 1] += out->off[(size_t)r];
-            out->total = out->off[(size_t)nreg];
-            if (out->table_id && out->store_base == 0) anchor_flags_h.assign(out->flags(), out->flags() + nok);      // (settle() lists the flagged rows from it)
-            break;
-        }
+        int rc;
+        for (int attempt = may_skip_waits ? 0 : 1; (rc = tail_attempt(c, attempt > 0)) == kRepeat; attempt++) {}
+        if (rc != kNext) return rc;
         collect_timing();
         return 0;
     }
 
+    // exchange 2 of a sharded run: the candidates' states in every genome, each rank's block from the rank that searched it (d_at).
+    // -> 0, or an error code
+    int exchange_states(SearchCall& c) {
+        const int nq = c.nq, lbits = c.lbits; const uint64_t ncand = c.ncand; const uint64_t* const scand = d_cand.p;
+        uint64_t* const skey = c.skey; uint64_t* const sval = c.sval;
+        ensure(d_at, (size_t)ncand * (size_t)nq);
+        be.launch("state_at_candidate", (int64_t)ncand * nq, StateAtCandidate{d_R.p, scand, ngen, skey, sval, d_lo.p, d_state.p, d_rep.p, lbits, d_at.p, d_cbase.p, d_coarse.p});
+        be.mark("exchange_states");
+        const size_t nqz = (size_t)nq, cz = (size_t)ncand;
+        const int widest = widest_block();
+        const size_t blk = cz * (size_t)widest;
+        if (coll.device) {      // pack this rank's columns, RCCL all-gather on the engine's stream, spread the blocks: nothing leaves the device
+            ensure(d_xsend, blk); ensure(d_xrecv, blk * (size_t)coll.world);
+            be.launch("pack_states", (int64_t)blk, PackStates{d_at.p, nq, g_first - 1, g_last - g_first, widest, d_xsend.p});
+            if (be.allgather_dev(d_xsend.p, (int64_t)(sizeof(GenomeAtK) * blk), d_xrecv.p)) { error = "RCCL all-gather of candidate states failed: " + be.error(); return -4; }
+            be.launch("unpack_states", (int64_t)(cz * nqz), UnpackStates{d_xrecv.p, nq, coll.world, widest, (int64_t)ncand, d_at.p});
+        } else {
+            std::vector<GenomeAtK> all(cz * nqz);
+            be.d2h(all.data(), d_at.p, sizeof(GenomeAtK) * all.size());
+            std::vector<GenomeAtK> send(blk), recv(blk * (size_t)coll.world);
+            const size_t mine = (size_t)(g_last - g_first);
+            for (size_t k = 0; k < cz; k++)
+                for (size_t x = 0; x < mine; x++) send[k * (size_t)widest + x] = all[k * nqz + (size_t)(g_first - 1) + x];
+            if (coll.allgather(coll.ctx, send.data(), (int64_t)(sizeof(GenomeAtK) * send.size()), recv.data())) { error = "all-gather of candidate states failed"; return -4; }
+            for (int r = 0; r < coll.world; r++) {
+                int a, b; shard_range(ngen, r, coll.world, &a, &b);
+                const GenomeAtK* src = recv.data() + (size_t)r * send.size();
+                for (size_t k = 0; k < cz; k++)
+                    for (int x = 0; x < b - a; x++) all[k * nqz + (size_t)(a - 1 + x)] = src[k * (size_t)widest + (size_t)x];
+            }
+            be.h2d(d_at.p, all.data(), sizeof(GenomeAtK) * all.size());
+        }
+        be.mark("fold");
+        return 0;
+    }
+
+    // One attempt at the tail.  exact: it waits for the candidate count and the accepted count (round trips 2 and 3); else it runs over
+    // capacities from the hint and returns kRepeat if one of them was too small, or the list is not the long list it was taken for.
+    int tail_attempt(SearchCall& c, const bool exact) {
+        const int64_t nreg = c.nreg, nwv = c.nwv; const int nq = c.nq, lbits = c.lbits; const GapBatch* const gb = c.gb; BatchResult* const out = c.out;
+        const bool from_store = c.from_store, sharded = c.sharded; CallHint& hint = *c.hint;
+        uint64_t* const skey = c.skey; uint64_t* const sval = c.sval; const int64_t* const ncand_p = c.ncand_p;
+        const int32_t& verdict = c.verdict;      // (a reference: the device exchange's verdict lands with the wait for the candidate count)
+        int64_t &ncand_i = c.ncand_i, &nok = c.nok; int64_t (&counts_h)[2] = c.counts_h; std::vector<int32_t>& reg_h = c.reg_h;
+        c.exact = exact;
+        ncand_i = 0;
+        if (exact) be.d2h(&ncand_i, ncand_p, 8);                                   // round trip 2: candidate count
+        if (verdict < 0) { budget_exceeded = true; error = "per-thread work budget exceeded on some rank (degenerate repeat structure in a region)"; return -5; }
+        if (exact) {
+            last_candidates = ncand_i;
+            if (ncand_i == 0) { hint.ncand = 1; hint.nok = 0; if (resident && from_store) out->store_base = ms_count; be.mark(nullptr); collect_timing(); return 0; }
+        }
+        // capacity of the candidate list: the count itself when it is known
+        const uint64_t ncand = c.ncand = exact ? (uint64_t)ncand_i : (uint64_t)(hint.ncand + hint.ncand / 8 + 256);
+        ensure(d_cand, (size_t)ncand);
+        be.launch("cand_write", nwv * 64, CandWrite{d_R.p, nreg, d_posbase.p, d_wmask.p, d_woff.p, d_cand.p, ncand});
+        const uint64_t* scand = d_cand.p;        // in (region, k) order by construction
+
+        // -- per-candidate genome fold
+        be.mark("fold");
+        ensure(d_ok, (size_t)ncand); ensure(d_ok_k, (size_t)ncand); ensure(d_ok_lon, (size_t)ncand);
+        ensure(d_osp, (size_t)ncand * (size_t)nq); ensure(d_ofwd, (size_t)ncand * (size_t)nq);
+        const GenomeAtK* at = nullptr;
+        if (sharded) {   // exchange 2: every rank contributes the (EP,UP,SP) columns of its genome block
+            if (int rc = exchange_states(c)) return rc;
+            at = d_at.p;
+        }
+        be.launch_wave("fold_candidates", xcd_grid((int64_t)ncand),
+                       FoldCandidates{d_R.p, scand, ngen, at, skey, sval, d_lo.p, d_state.p, d_rep.p, lbits, d_cbase.p, d_coarse.p,
+                                      d_ok_k.p, d_ok_lon.p, d_osp.p, d_ofwd.p, d_ok.p, (int64_t)ncand, ncand_p});
+
+        // -- accepted candidates, compacted on the device and downloaded straight into the result's blocks
+        be.mark("compact");
+        ensure(d_okcnt, (size_t)ncand + 1); ensure(d_okpos, (size_t)ncand + 1);
+        be.launch("ok_count", (int64_t)ncand + 1, OkCount{d_ok.p, ncand_p, d_okcnt.p, (int64_t)ncand});
+        be.exclusive_scan(d_okcnt.p, d_okpos.p, (size_t)ncand + 1);
+        const int64_t* nok_p = c.nok_p = d_okpos.p + ncand;      // the accepted count, where the device keeps it
+        nok = 0;
+        if (exact) be.d2h(&nok, nok_p, 8);                                    // round trip 3: accepted count
+        // capacity of the accepted rows: the count itself when it is known, else every candidate could be accepted
+        const size_t nokz = c.nokz = exact ? (size_t)nok : (size_t)ncand;
+        ensure(d_creg, std::max<size_t>(nokz, 1)); ensure(d_ck, std::max<size_t>(nokz, 1)); ensure(d_clon, std::max<size_t>(nokz, 1));
+        reg_h.assign(nokz, 0);
+        out->release();
+        out->kb = pool->take(4 * nokz); out->lonb = pool->take(4 * nokz);
+        out->rows = want_rows; out->dirty_known = false; out->table_id = 0; out->store_base = -1;
+        const StoreCounts before = store_mark();
+        c.anchor_call = false;
+        if (!want_rows) compact_sp(c); else compact_rows(c);
+        be.d2h_async(reg_h.data(), d_creg.p, 4 * nokz);
+        be.d2h_async(out->kb.p, d_ck.p, 4 * nokz);
+        counts_h[0] = ncand_i; counts_h[1] = nok;
+        if (!exact) { be.d2h_async(&counts_h[0], ncand_p, 8); be.d2h_async(&counts_h[1], nok_p, 8); }
+        flush_downloads();
+        be.mark(nullptr);
+        be.sync();                                                         // round trip 4: the results (and, where the call did not wait for them, the two counts)
+        const bool anchor_call = c.anchor_call;
+        if (!exact) {
+            ncand_i = counts_h[0]; nok = counts_h[1];
+            const bool fits = (uint64_t)ncand_i <= ncand && anchor_call == (nreg == 1 && !gb && nok >= dirty_min);
+            if (!fits) {      // the capacity was too small, or the list is not the long list it was taken for: again, with the counts
+                store_rewind(before);
+                tail_repeats++;
+                be.mark("candidates");
+                return kRepeat;
+            }
+            last_candidates = ncand_i;
+            if (out->store_base >= 0) ms_count = out->store_base + nok;
+        }
+        hint.ncand = std::max<int64_t>(ncand_i, 1); hint.nok = nok;
+        last_accepted = nok;
+        if (anchor_call) { anchor_table_rows = nok; anchor_table_id = out->table_id; }
+        for (int64_t w = 0; w < nok; w++) out->off[(size_t)reg_h[(size_t)w] + 1]++;
+        for (int64_t r = 0; r < nreg; r++) out->off[(size_t)r + 1] += out->off[(size_t)r];
+        out->total = out->off[(size_t)nreg];
+        if (out->table_id && out->store_base == 0) anchor_flags_h.assign(out->flags(), out->flags() + nok);      // (settle() lists the flagged rows from it)
+        return kNext;
+    }
+
+    // the accepted candidates as (sp, fwd) rows, and their downloads
+    void compact_sp(SearchCall& c) {
+        const int nq = c.nq; const uint64_t ncand = c.ncand; const size_t nokz = c.nokz, nqz2 = (size_t)nq; BatchResult* const out = c.out;
+        const uint64_t* const scand = d_cand.p; const int64_t* const ncand_p = c.ncand_p;
+        ensure(d_csp, std::max<size_t>(nokz * nqz2, 1)); ensure(d_cfwd, std::max<size_t>(nokz * nqz2, 1));
+        be.launch("compact_sp", (int64_t)ncand * nq,
+                  CompactSp{scand, d_ok.p, d_okpos.p, nq, d_ok_k.p, d_ok_lon.p, d_osp.p, d_ofwd.p, d_creg.p, d_ck.p, d_clon.p, d_csp.p, d_cfwd.p, ncand_p});
+        be.mark("download");
+        group_downloads();
+        out->spb = pool->take(4 * nokz * nqz2); out->fwdb = pool->take(nokz * nqz2);
+        be.d2h_async(out->spb.p, d_csp.p, 4 * nokz * nqz2);
+        be.d2h_async(out->fwdb.p, d_cfwd.p, nokz * nqz2);
+        be.d2h_async(out->lonb.p, d_clon.p, 4 * nokz);
+    }
+
+    // the accepted candidates as MUM rows (start, strand, flags), into the MUM store where they stay on the device; their downloads
+    void compact_rows(SearchCall& c) {
+        const int64_t nreg = c.nreg; const GapBatch* const gb = c.gb; const bool from_store = c.from_store, exact = c.exact, anchor_guess = c.anchor_guess;
+        const int64_t nok = c.nok; const uint64_t ncand = c.ncand; const size_t nokz = c.nokz, ngz = (size_t)ngen; BatchResult* const out = c.out;
+        const uint64_t* const scand = d_cand.p; const int64_t* const ncand_p = c.ncand_p; const int64_t* const nok_p = c.nok_p;
+        bool& anchor_call = c.anchor_call;
+        // Resident mode (pm_session_rows(s, 2)): the rows of the anchor call, and of every search of regions of the region store,
+        // stay on the device as rows of the MUM store -- the host receives the per-row scalars only (flags, k, length).  The
+        // anchor call's rows are the session's anchor table (= rows [0, A) of the store) in either mode.  The compaction
+        // writes such rows straight into the store (a copy of the 60 MB anchor table is half a millisecond).
+        anchor_call = nreg == 1 && !gb && (exact ? nok >= dirty_min : anchor_guess);
+        const bool keep_rows = resident && (anchor_call || from_store);
+        const bool to_store = anchor_call || keep_rows;
+        int32_t* p_start; uint8_t* p_strand; int32_t* p_lon; uint32_t* p_flags;
+        if (to_store) {
+            if (anchor_call) store_reset();
+            const size_t base = (size_t)ms_count, upto = base + nokz;
+            ensure_keep(d_anchor_start, std::max<size_t>(upto * ngz, 1), base * ngz); ensure_keep(d_ms_strand, std::max<size_t>(upto * ngz, 1), base * ngz);
+            ensure_keep(d_anchor_lon, std::max<size_t>(upto, 1), base); ensure_keep(d_anchor_flags, std::max<size_t>(upto, 1), base);
+            ensure_keep(d_ms_shift, std::max<size_t>(upto, 1), base); ensure_keep(d_ms_len, std::max<size_t>(upto, 1), base); ensure_keep(d_ms_state, std::max<size_t>(upto, 1), base);
+            p_start = d_anchor_start.p + base * ngz; p_strand = d_ms_strand.p + base * ngz; p_lon = d_anchor_lon.p + base; p_flags = d_anchor_flags.p + base;
+            out->store_base = (int64_t)base;
+            ms_count = (int64_t)upto;      // (capacity: set to base + the accepted count once that is known)
+        } else {
+            ensure(d_csp, std::max<size_t>(nokz * ngz, 1)); ensure(d_cfwd, std::max<size_t>(nokz * ngz, 1)); ensure(d_cflags, std::max<size_t>(nokz, 1));
+            p_start = d_csp.p; p_strand = d_cfwd.p; p_lon = d_clon.p; p_flags = d_cflags.p;
+        }
+        const bool long_list = nreg == 1 && (exact ? nok >= dirty_min : anchor_guess);
+        if (long_list) ensure(d_dirty, nokz);
+        {      // the flags of the rows (OR-ed into), the cheap overlap test's marks, shift and state of the new store rows: one launch
+            const ClearJob jobs[] = {{p_flags, 4 * nokz, 0}, {long_list ? d_dirty.p : nullptr, long_list ? 4 * nokz : 0, 0},
+                                     {to_store ? d_ms_shift.p + (ms_count - (int64_t)nokz) : nullptr, to_store ? 4 * nokz : 0, 0},
+                                     {to_store ? d_ms_state.p + (ms_count - (int64_t)nokz) : nullptr, to_store ? nokz : 0, 0}};
+            be.clear_many(jobs, 4);
+        }
+        be.launch("compact_candidates", (int64_t)ncand * ngen,
+                  CompactCandidates{scand, d_ok.p, d_okpos.p, ngen, d_ok_k.p, d_ok_lon.p, d_osp.p, d_ofwd.p, d_starts.p, d_lens.p, d_glen,
+                                    d_creg.p, d_ck.p, p_lon, p_start, p_strand, p_flags, ncand_p});
+        if (long_list) {     // a long list of one region (the anchor call): the cheap overlap test on the device
+            const int64_t nblocks = ((int64_t)nokz + kDirtyBlock - 1) / kDirtyBlock, groups = (ngen + 63) / 64;
+            ensure(d_bmax, (size_t)nblocks * ngz); ensure(d_bmin, (size_t)nblocks * ngz);
+            be.launch_wave("dirty_extent", nblocks * groups, DirtyExtent{p_start, p_lon, p_flags, nok_p, ngen, d_bmax.p, d_bmin.p});
+            be.launch_wave("dirty_prefix", groups, DirtyPrefix{nblocks, ngen, d_bmax.p, d_bmin.p});
+            be.launch_wave("dirty_mark", nblocks * groups, DirtyMark{p_start, p_lon, nok_p, ngen, d_bmax.p, d_bmin.p, p_flags, d_dirty.p});
+            be.launch("dirty_merge", (int64_t)nokz, DirtyMerge{d_dirty.p, p_flags, nok_p});
+            out->dirty_known = true;
+        }
+        if (to_store) {
+            be.d2d(d_ms_len.p + (ms_count - (int64_t)nokz), p_lon, 4 * nokz);
+            if (anchor_call) out->table_id = ++table_counter;
+        }
+        be.mark("download");
+        group_downloads();      // (flags, lengths, regions, k and the two counts: one launch instead of seven copies)
+        out->flagsb = pool->take(4 * nokz);
+        be.d2h_async(out->flagsb.p, p_flags, 4 * nokz);
+        if (!keep_rows) {
+            out->startb = pool->take(4 * nokz * ngz); out->strandb = pool->take(nokz * ngz);
+            be.d2h_async(out->startb.p, p_start, 4 * nokz * ngz);
+            be.d2h_async(out->strandb.p, p_strand, nokz * ngz);
+        }
+        be.d2h_async(out->lonb.p, p_lon, 4 * nokz);
+    }
+
+public:
 
     // =====================================================================================================================
     // The resident route (store_kernels.h; include/parsnp_mum.h: pm_store_*): what the reference does with the candidate lists
@@ -896,7 +1068,12 @@ public:
     std::vector<uint32_t> anchor_flags_h;
     static constexpr int kAgain = -6; // PM_EAGAIN: the resident route does not apply; the caller takes the host route
 
-    void begin_store_call() { timing.clear(); last_events = last_rest = last_positions = last_candidates = last_accepted = last_grouped = last_grouped_wide = last_wide_regions = 0; last_handed_back = -1; last_index_bucketed = last_index_overflow = 0; last_index_lost = -1; last_alg[0] = last_alg[1] = last_alg[2] = 0; }      // (counts of the last search travel with pm_last_timing)
+    // "nothing of the last call": the counts of a search that travel with pm_last_timing (a search sets last_events and last_rest itself)
+    void reset_call_counts() {
+        last_positions = last_candidates = last_accepted = last_grouped = last_grouped_wide = last_wide_regions = 0; last_handed_back = -1;
+        last_index_bucketed = last_index_overflow = 0; last_index_lost = -1; last_alg[0] = last_alg[1] = last_alg[2] = 0;
+    }
+    void begin_store_call() { timing.clear(); last_events = last_rest = 0; reset_call_counts(); }
     Store store_view() { return Store{d_anchor_start.p, d_ms_strand.p, d_anchor_lon.p, d_anchor_flags.p, d_ms_shift.p, d_ms_len.p, d_ms_state.p, ngen}; }
     // coherent: the reader must see marks made while its kernel runs (a wavefront that validates candidates in order)
     Layout layout_view(uint64_t* image, bool coherent = true) { return Layout{image, d_lay_off.p, d_lay_bits.p, coherent ? 1 : 0}; }
@@ -1248,18 +1425,18 @@ public:
                 defer = d_v_defer.p;
                 exact_cluster_tests++;
             } else be.launch_wave("clusters_disjoint", ncl - 1, ClustersDisjoint{ngen, d_rg_start.p, d_rg_len.p, d_list.p, d_v_first.p, d_rg_count.p + 3, stage_first, force_unsure ? 1 : 0});
-            be.launch_wave("cluster_validate", xcd_grid(na),
-                           ClusterValidate{store_view(), layout_view(d_image.p), P, d_rg_start.p, d_rg_len.p, d_rg_info.p, d_rg_count.p, (uint64_t)cap,
-                                           d_list.p, d_v_row0.p, d_list2.p, d_v_first.p, q, (uint32_t*)(d_rg_count.p + 1), na, 0, nullptr, d_rg_count.p + 3,
-                                           d_foreign.p, d_foreign_count.p, (uint64_t)foreign_cap, d_foreign_masks.p, d_ms_key.p, generation_no, d_recwords.p, defer, d_v_done.p,
-                                           d_rg_pkey.p, d_outw.p, d_outw_count.p, (uint64_t)kOutwCap});
+            // a stage of the call: `count` clusters from cluster `first` on, behind `gate` (nullptr: none), as generation `gen`
+            auto validate = [&](int64_t count, int64_t first, const uint64_t* gate, int32_t gen) {
+                be.launch_wave("cluster_validate", xcd_grid(count),
+                               ClusterValidate{store_view(), layout_view(d_image.p), P, d_rg_start.p, d_rg_len.p, d_rg_info.p, d_rg_count.p, (uint64_t)cap,
+                                               d_list.p, d_v_row0.p, d_list2.p, d_v_first.p, q, (uint32_t*)(d_rg_count.p + 1), count, first, gate, d_rg_count.p + 3,
+                                               d_foreign.p, d_foreign_count.p, (uint64_t)foreign_cap, d_foreign_masks.p, d_ms_key.p, gen, d_recwords.p, defer, d_v_done.p,
+                                               d_rg_pkey.p, d_outw.p, d_outw_count.p, (uint64_t)kOutwCap});
+            };
+            validate(na, 0, nullptr, generation_no);
             if (stage_first > 0) {
                 be.launch("stage_gate", 1, StageGate{d_rg_count.p, (uint64_t)rg_count, force_gate ? 1 : 0});
-                be.launch_wave("cluster_validate", xcd_grid(ncl - na),
-                               ClusterValidate{store_view(), layout_view(d_image.p), P, d_rg_start.p, d_rg_len.p, d_rg_info.p, d_rg_count.p, (uint64_t)cap,
-                                               d_list.p, d_v_row0.p, d_list2.p, d_v_first.p, q, (uint32_t*)(d_rg_count.p + 1), ncl - na, na, d_rg_count.p + 2, d_rg_count.p + 3,
-                                               d_foreign.p, d_foreign_count.p, (uint64_t)foreign_cap, d_foreign_masks.p, d_ms_key.p, generation_no + 1, d_recwords.p, defer, d_v_done.p,
-                                               d_rg_pkey.p, d_outw.p, d_outw_count.p, (uint64_t)kOutwCap});
+                validate(ncl - na, na, d_rg_count.p + 2, generation_no + 1);
             }
             be.launch_wave("outside_write_check", kOutwWaves,
                            OutsideWriteCheck{store_view(), d_rg_start.p, d_rg_len.p, d_rg_info.p, d_rg_pkey.p, d_rg_count.p, (uint64_t)cap, d_list.p, d_outw.p, d_outw_count.p, (uint64_t)kOutwCap,
@@ -1793,13 +1970,9 @@ private:
     void flush_downloads() { flush_on(be, 0); }
 
     SeqBlock* blk = nullptr; int64_t* d_goff = nullptr; int64_t* d_glen = nullptr;
-    int64_t total_words = 0;
     Packed P{};
-    size_t ev_cap_hint = 0, cand_cap_hint = 0, rest_cap_hint[2] = {0, 0}, grp_cap_hint = 0;
-    // what call number `i` of the last step needed (i = 0: the anchor call; then the searches of store regions in their order): the
-    // capacities call i of this step launches over instead of waiting for its counts
-    struct CallHint { int64_t units = 0, ncand = 0, nok = 0; };
-    std::vector<CallHint> call_hints;
+    size_t ev_cap_hint = 0, rest_cap_hint[2] = {0, 0}, grp_cap_hint = 0;
+    std::vector<CallHint> call_hints;      // by call number of the step
     int64_t call_ordinal = 0;      // candidates / accepted rows of the last call of a shape ([1]: one region = an anchor call): capacities of the next one's tail
     Buf<uint8_t> d_gflag; Buf<int64_t> d_glo;
     Buf<int64_t> d_bkbase, d_bkbegin, d_ovf; Buf<uint64_t> d_ikey, d_ikey2, d_ikey3, d_ikey4;      // the bucket build of the index: first bucket per region, first record per bucket, overflow list, keys
