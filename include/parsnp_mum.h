@@ -337,6 +337,23 @@ int pm_store_layout(pm_session* s, uint64_t* out, int64_t words);
  * `unalign_write` in pm_last_timing. */
 int pm_store_unalign_count(pm_session* s, int64_t* all_runs, int64_t* kept_runs);
 int pm_store_unalign_runs(pm_session* s, int32_t* start, int32_t* end, int32_t* ordinal, int64_t n);
+/* Core-genome SNP columns and pairwise SNP distances of alignment columns the caller hands over in chunks of n_rows rows.  Judged
+ * case-insensitively, a column is a CORE SNP when every row holds one of A C G T and at least two different letters occur, CORE
+ * INVARIANT when every row holds the same one of the four, and OTHER when some row holds anything else ('-', 'N', ...).  n_rows is
+ * independent of the session's genomes.  A collection is started with its row count (an earlier one is forgotten); an add takes
+ * row i of its chunk at chars + i * pitch (ASCII, any case), numbers the columns across adds in the order added, and reports the
+ * running counts (totals may be NULL; n_cols == 0 is a valid add); the columns call gives col[v], the index of core SNP v among all
+ * columns added, and letters, n_rows x core_snps, row-major, upper case (either may be NULL; nothing is written for no core SNP);
+ * the distances call gives dist, n_rows x n_rows, row-major: the number of core SNP columns in which two rows differ.
+ * PM_EINVAL: n_rows < 2, pitch < n_cols, n_cols < 0, chars NULL with n_cols > 0, any call before a collection was started.
+ * PM_ELIMIT: more rows than the limits call reports (2 048; it needs no device), or 2^31 or more columns in all.  Phases
+ * `snp_classify`, `snp_scan`, `snp_pack` and `snp_dist` in pm_last_timing. */
+typedef struct pm_snp_counts { int64_t columns, core_invariant, core_snps, other; } pm_snp_counts;
+int pm_snp_limits(int* max_rows);
+int pm_snp_begin(pm_session* s, int32_t n_rows);
+int pm_snp_add(pm_session* s, int64_t n_cols, int64_t pitch, const uint8_t* chars, pm_snp_counts* totals);
+int pm_snp_columns(pm_session* s, int64_t* col, uint8_t* letters);
+int pm_snp_distances(pm_session* s, int32_t* dist);
 /* bytes this session has moved over the host link so far (every copy the engine issued, both directions) */
 int pm_session_traffic(const pm_session* s, uint64_t* h2d_bytes, uint64_t* d2h_bytes);
 

@@ -73,6 +73,14 @@ class Lib:
         self._check(self.L.pm_group_limits(C.c_int(1 if wide else 0), C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
 
+    def snp_limits(self):
+        """rows a SNP collection takes (Session.core_snps): pm_snp_limits"""
+        if not hasattr(self.L, "pm_snp_limits"):
+            raise PmError("this provider of the ABI has no pm_snp_limits")
+        a = C.c_int()
+        self._check(self.L.pm_snp_limits(C.byref(a)))
+        return a.value
+
     def _gap_limits_of(self, name):
         if not hasattr(self.L, name):
             raise PmError("this provider of the ABI has no %s" % name)
@@ -159,6 +167,35 @@ class Session:
         self.lib._check(L.pm_store_unalign_runs(self.h, ptr(start), ptr(end), ptr(ordinal), total))
         at = np.concatenate([[0], np.cumsum(kept)])
         return [(start[at[j]:at[j + 1]], end[at[j]:at[j + 1]], ordinal[at[j]:at[j + 1]]) for j in range(self.n)], all_runs, kept
+
+    def core_snps(self, chunks, n_rows=None):
+        """pm_snp_begin, a pm_snp_add per chunk, pm_snp_columns, pm_snp_distances -> (counts, col, letters, dist).  chunks: uint8
+        arrays of shape (n_rows, w), ASCII; a view whose rows lie further apart than w bytes (a slice of a wider array) is handed
+        over as it lies, with its row stride as the pitch.  counts: dict of columns, core_invariant, core_snps, other; col: int64
+        [V], the index of every core SNP column among all columns; letters: uint8 [n_rows, V], upper case; dist: int32 [n_rows, n_rows]"""
+        L = self.lib.L
+        if not hasattr(L, "pm_snp_begin"):
+            raise PmError("this provider of the ABI has no pm_snp_begin")
+        v = C.c_void_p
+        L.pm_snp_begin.argtypes = [v, C.c_int32]
+        L.pm_snp_add.argtypes = [v, C.c_int64, C.c_int64, v, v]
+        L.pm_snp_columns.argtypes = [v, v, v]
+        L.pm_snp_distances.argtypes = [v, v]
+        n = int(chunks[0].shape[0]) if n_rows is None else int(n_rows)
+        self.lib._check(L.pm_snp_begin(self.h, n))
+        totals = np.zeros(4, np.int64)
+        for ch in chunks:
+            assert ch.dtype == np.uint8 and ch.ndim == 2 and ch.shape[0] == n
+            w = int(ch.shape[1])
+            if w and not (ch.strides[1] == 1 and ch.strides[0] >= w):
+                ch = np.ascontiguousarray(ch)
+            pitch = int(ch.strides[0]) if w else 0
+            self.lib._check(L.pm_snp_add(self.h, w, pitch, ch.ctypes.data_as(v) if w else None, totals.ctypes.data_as(v)))
+        nv = int(totals[2])
+        col, letters, dist = np.zeros(nv, np.int64), np.zeros((n, nv), np.uint8), np.zeros((n, n), np.int32)
+        self.lib._check(L.pm_snp_columns(self.h, col.ctypes.data_as(v), letters.ctypes.data_as(v)))
+        self.lib._check(L.pm_snp_distances(self.h, dist.ctypes.data_as(v)))
+        return dict(zip(("columns", "core_invariant", "core_snps", "other"), (int(x) for x in totals))), col, letters, dist
 
     def __enter__(self):
         return self

@@ -280,6 +280,28 @@ int pm_store_unalign_runs(pm_session* s, int32_t* start, int32_t* end, int32_t* 
     if (!s || n < 0 || n >= ((int64_t)1 << 31) || (n > 0 && (!start || !end || !ordinal))) return fail(PM_EINVAL, "bad argument");
     PM_STORE_CALL(s->engine->store_unalign_write(start, end, ordinal, n))
 }
+// core SNP columns and SNP distances (snp_kernels.h)
+static_assert(sizeof(pm_snp_counts) == 4 * sizeof(int64_t), "pm_snp_counts");
+int pm_snp_limits(int* max_rows) {
+    if (max_rows) *max_rows = pm::kSnpMaxRows;
+    return PM_OK;
+}
+int pm_snp_begin(pm_session* s, int32_t n_rows) {
+    if (!s) return fail(PM_EINVAL, "bad argument");
+    PM_STORE_CALL(s->engine->snp_begin(n_rows))
+}
+int pm_snp_add(pm_session* s, int64_t n_cols, int64_t pitch, const uint8_t* chars, pm_snp_counts* totals) {
+    if (!s || n_cols < 0 || pitch < n_cols || (n_cols > 0 && !chars)) return fail(PM_EINVAL, "bad argument");
+    PM_STORE_CALL(s->engine->snp_add(n_cols, pitch, chars, (int64_t*)totals))
+}
+int pm_snp_columns(pm_session* s, int64_t* col, uint8_t* letters) {
+    if (!s) return fail(PM_EINVAL, "bad argument");
+    PM_STORE_CALL(s->engine->snp_columns(col, letters))
+}
+int pm_snp_distances(pm_session* s, int32_t* dist) {
+    if (!s || !dist) return fail(PM_EINVAL, "bad argument");
+    PM_STORE_CALL(s->engine->snp_distances(dist))
+}
 int pm_session_traffic(const pm_session* s, uint64_t* h2d_bytes, uint64_t* d2h_bytes) {
     if (!s) return PM_EINVAL;
     if (h2d_bytes) *h2d_bytes = s->backend->bytes_h2d;

@@ -28,6 +28,7 @@
 #include "store_kernels.h"
 #include "dense_kernels.h"
 #include "index_kernels.h"
+#include "snp_kernels.h"
 
 namespace pm {
 
@@ -1781,6 +1782,96 @@ public:
     }
     std::vector<int64_t> un_blk_h;
 
+    // Core SNP columns and SNP distances (snp_kernels.h).  A collection is independent of the session's genomes: n rows, columns
+    // added chunk by chunk.  Every add waits once, for its counts: the planes grow by the chunk's core SNPs, not by its columns.
+    int snp_begin(int32_t n_rows) {
+        if (n_rows < 2) { error = "a SNP collection needs at least 2 rows"; return -2; }
+        if (n_rows > kSnpMaxRows) { error = "a SNP collection takes at most " + std::to_string(kSnpMaxRows) + " rows"; return -5; }
+        snp_rows = n_rows; snp_cols = 0; snp_v = 0; snp_up_bytes = 0;
+        ensure(d_snp_counts, 4);
+        ClearJob job{d_snp_counts.p, 4 * sizeof(uint64_t), 0};
+        be.clear_many(&job, 1);
+        return 0;
+    }
+    int snp_add(int64_t n_cols, int64_t pitch, const uint8_t* chars, int64_t* totals) {
+        if (snp_rows < 2) { error = "no SNP collection has been started"; return -2; }
+        if (snp_cols + n_cols >= ((int64_t)1 << 31)) { error = "a SNP collection takes fewer than 2^31 columns"; return -5; }
+        timing.clear();
+        const size_t n = (size_t)snp_rows, nc = (size_t)n_cols;
+        uint64_t counts[4] = {0, 0, 0, 0};
+        if (n_cols) {
+            // the chunk, its rows packed side by side (pitch n_cols on the device), through the page-locked staging block
+            uint8_t* stage = (uint8_t*)be.staging(n * nc);
+            if (!stage) throw DeviceOutOfMemory{n * nc};
+            for (size_t r = 0; r < n; r++) memcpy(stage + r * nc, chars + r * (size_t)pitch, nc);
+            ensure(d_snp_chunk, n * nc); ensure(d_snp_flag, nc + 1); ensure(d_snp_rank, nc + 1);
+            be.h2d_staged(d_snp_chunk.p, stage, n * nc);
+            snp_up_bytes += n * nc;
+            be.mark("snp_classify");
+            be.launch("snp_classify", n_cols, SnpClassify{d_snp_chunk.p, n_cols, n_cols, snp_rows, d_snp_flag.p, d_snp_counts.p});
+            be.mark("snp_scan");
+            be.exclusive_scan(d_snp_flag.p, d_snp_rank.p, nc + 1);
+            be.mark(nullptr);
+        }
+        be.d2h(counts, d_snp_counts.p, sizeof counts);
+        const int64_t v1 = (int64_t)counts[1];
+        if (v1 > snp_v) {
+            const size_t w0 = (size_t)((snp_v + 63) / 64), w1 = (size_t)((v1 + 63) / 64);
+            ensure_keep(d_snp_col, (size_t)v1, (size_t)snp_v);
+            ensure_keep(d_snp_lo, w1 * n, w0 * n); ensure_keep(d_snp_hi, w1 * n, w0 * n);
+            be.mark("snp_pack");
+            be.launch("snp_rank", n_cols, SnpRank{d_snp_flag.p, d_snp_rank.p, snp_v, snp_cols, d_snp_col.p});
+            be.launch_wave("snp_pack", (int64_t)w1 - snp_v / 64, SnpPack{d_snp_chunk.p, n_cols, snp_rows, d_snp_col.p, snp_cols, snp_v, v1, d_snp_lo.p, d_snp_hi.p});
+            be.mark(nullptr);
+            be.sync();      // (the staging block and the chunk are free for the next add)
+            snp_v = v1;
+        }
+        snp_cols += n_cols;
+        collect_timing_more();
+        if (totals) { totals[0] = snp_cols; totals[1] = (int64_t)counts[0]; totals[2] = (int64_t)counts[1]; totals[3] = (int64_t)counts[2]; }
+        return 0;
+    }
+    int64_t snp_core() const { return snp_v; }
+    // col[v]: the index of core SNP v among all columns added; letters: n_rows x V, row-major, upper case (either may be null)
+    int snp_columns(int64_t* col, uint8_t* letters) {
+        if (snp_rows < 2) { error = "no SNP collection has been started"; return -2; }
+        if (!snp_v) return 0;
+        const size_t n = (size_t)snp_rows, v = (size_t)snp_v, words = (v + 63) / 64;
+        if (col) be.d2h_async(col, d_snp_col.p, 8 * v);
+        std::vector<uint64_t> lo, hi;
+        if (letters) {
+            lo.resize(words * n); hi.resize(words * n);
+            be.d2h_async(lo.data(), d_snp_lo.p, 8 * words * n); be.d2h_async(hi.data(), d_snp_hi.p, 8 * words * n);
+        }
+        be.sync();
+        if (letters)
+            for (size_t r = 0; r < n; r++)
+                for (size_t w = 0; w < words; w++) {
+                    const uint64_t l = lo[w * n + r], h = hi[w * n + r];
+                    const size_t upto = std::min<size_t>(64, v - w * 64);
+                    for (size_t t = 0; t < upto; t++) letters[r * v + w * 64 + t] = snp_letter((uint32_t)(((l >> t) & 1) | (((h >> t) & 1) << 1)));
+                }
+        return 0;
+    }
+    // dist: n_rows x n_rows, row-major
+    int snp_distances(int32_t* dist) {
+        if (snp_rows < 2) { error = "no SNP collection has been started"; return -2; }
+        const size_t n = (size_t)snp_rows;
+        if (!snp_v) { memset(dist, 0, 4 * n * n); return 0; }
+        timing.clear();
+        ensure(d_snp_dist, n * n);
+        const int32_t tiles = (snp_rows + kSnpTile - 1) / kSnpTile;
+        const int64_t words = (snp_v + 63) / 64;
+        const uint64_t last_mask = (snp_v & 63) ? ((1ull << (snp_v & 63)) - 1) : ~0ull;
+        be.mark("snp_dist");
+        be.launch_wave("snp_dist", (int64_t)tiles * tiles, SnpDist{d_snp_lo.p, d_snp_hi.p, snp_rows, words, last_mask, tiles, d_snp_dist.p});
+        be.mark(nullptr);
+        be.d2h(dist, d_snp_dist.p, 4 * n * n);
+        collect_timing_more();
+        return 0;
+    }
+    int32_t snp_rows = 0; int64_t snp_cols = 0, snp_v = 0; uint64_t snp_up_bytes = 0;
+
     // The suffix array of the flagged regions of a batch (dense_kernels.h) and their rep' (after RepeatLength, which skipped them).
     // One segmented prefix-doubling sort over all of them; every round waits for its count of distinct ranks (8 bytes) -- a round
     // trip per round, on this path only.
@@ -1996,6 +2087,7 @@ private:
     int64_t table_counter = 0;
     Buf<uint64_t> d_image;
     Buf<int64_t> d_un_blk, d_un_cnt, d_un_scan, d_un_tot; Buf<int32_t> d_un_out;      // the unaligned runs: block geometry, counts per block, their scans, totals per genome, the runs
+    Buf<uint64_t> d_snp_counts, d_snp_lo, d_snp_hi; Buf<uint8_t> d_snp_chunk; Buf<int64_t> d_snp_flag, d_snp_rank, d_snp_col; Buf<int32_t> d_snp_dist;      // the SNP collection (snp_kernels.h)
     Buf<uint8_t> d_ms_strand, d_ms_state, d_small8, d_o_strand; Buf<int32_t> d_ms_shift, d_ms_len, d_list, d_list2, d_j_min, d_j_max, d_o_start;
     Buf<int64_t> d_rg_start, d_rg_len, d_lay_off, d_lay_bits, d_v_row0, d_v_first, d_f_start, d_f_end, d_f_pack; Buf<RegInfo> d_rg_info; Buf<uint64_t> d_rg_count, d_once, d_twice;
     Buf<RowInfo> d_rowinfo; Buf<uint64_t> d_alg;

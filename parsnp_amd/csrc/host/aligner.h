@@ -48,6 +48,7 @@ inline double cpu_lap_s() {
 struct Params {
     int c = 0, d = 0, q = 0, p = 0, do_align = 0, cores = 2, random = 0;
     bool unaligned = false, recomb_filter = false, anchors_only = false, calc_mumi = false, extend_mums = false;
+    bool snps = false;      // [Output] snps: core SNP columns and SNP distances beside the XMFA (snps.cpp); the reference ignores the key
     float diag_diff = 1.0f, factor = 0.0f;
     std::string anchors, mums, anchorfile, mumfile, prefix, outdir;
 };
@@ -357,6 +358,7 @@ public:
     const std::string& resident_why() const { return res_.why; }
     bool resident_chain();                               // phases C-D from the device (resident.cpp); false: the caller runs them
     void materialize();                                  // rows of the LCBs' MUMs for the writer; no-op on the host route
+    pm_session* session() const { return session_; }      // (the writer's SNP collection runs on it)
     void unaligned_runs(UnalignRuns* out);               // the runs parsnp.unalign lists: from the device's layout on the resident route, from `layout` otherwise
     void attach_layout_image();                          // resident route: the device's layout fetched into `layout` (the bit-by-bit checker of parsnp.unalign, a test hook)
     // After resident_chain() returned true `mums` and `lcbs` are NOT written yet: the device's answer is kept (Resident::chain_*)
@@ -505,6 +507,40 @@ int64_t scan_unaligned_words(const uint64_t* w, int64_t nbits, std::vector<int32
 // what the last write_unaligned did (PARSNP_TIMING: unalign_*)
 struct UnalignCounts { double s = 0; long runs = 0, kept = 0; double device_ms = 0, d2h_bytes = 0; };
 extern UnalignCounts unalign_counts;
+
+// Core SNP columns and SNP distances of the XMFA being written ([Output] snps=1; snps.cpp).  The writer hands over, LCB by LCB in
+// print order, the columns that are not MUM columns as blocks of n rows; MUM columns are core invariant by construction and are
+// only counted.  The blocks lie side by side in a staging matrix that goes to the engine (pm_snp_add) whenever it is full; after
+// the last one the core SNP columns and the distances come back and are mapped to (cluster, column, reference position).
+struct SnpCounts { bool on = false; long columns = 0, invariant = 0, core = 0, other = 0; double h2d_bytes = 0, scan_ms = 0, dist_ms = 0; };
+extern SnpCounts snp_counts;      // what the last write_output collected (PARSNP_TIMING: snp_*, with snps=1 only)
+int snp_max_rows();               // sequences a run with snps=1 may have
+class SnpCollector {
+public:
+    SnpCollector(pm_session* session, size_t n_rows, int threads);
+    void add_invariant(long cols) { invariant_ += cols; }
+    // `width` columns of the LCB printed as cluster<cluster>, the first one its column c0.  row(i, dst) writes the width characters of
+    // row i (any thread).  ref_pos: the reference position of every column, or null: ref_base + the characters other than '-' of row
+    // 0 to the left, inside the block.  Returns the characters other than '-' of row 0 in the block.
+    long add_block(int cluster, long c0, size_t width, const std::function<void(size_t, uint8_t*)>& row, const int64_t* ref_pos, int64_t ref_base);
+    // the same in steps, for many blocks at once: room for `width` columns side by side (row i at the returned pointer + i * pitch();
+    // what was staged before goes to the engine first when they do not fit), which the caller fills, then a commit per block, in order
+    size_t pitch() const { return pitch_; }
+    uint8_t* reserve(size_t width);
+    long commit(int cluster, long c0, size_t width, const int64_t* ref_pos, int64_t ref_base);
+    // the three files beside the XMFA, the console line, snp_counts
+    void finish(const std::vector<Genome>& genomes, const std::string& dir, const std::string& stem);
+
+private:
+    struct Entry { int64_t first; int32_t cluster; int32_t width; int64_t c0; };      // columns [first, first + width) of all columns handed over
+    void flush();
+    pm_session* session_; size_t n_; int threads_;
+    std::vector<uint8_t> stage_; size_t pitch_ = 0, used_ = 0;
+    std::vector<Entry> entries_; std::vector<int64_t> ref_pos_;
+    int64_t total_ = 0; long invariant_ = 0;
+    pm_snp_counts counts_{0, 0, 0, 0};
+    double scan_ms_ = 0, h2d_bytes_ = 0;
+};
 
 std::string reverse_complement(const std::string& s);   // Aligner::reversec, :1294-1393
 

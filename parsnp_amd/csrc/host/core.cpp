@@ -45,6 +45,7 @@ int CoreRun::open(const std::string& ini_path) {
     prm.factor = (float)ini.get_double("MUM", "factor");
     prm.prefix = ini.get("Output", "prefix", "parsnp");
     prm.outdir = ini.get("Output", "outdir", "output");
+    prm.snps = ini.get_bool("Output", "snps");
     const bool reverse_ref = ini.get_bool("Reference", "reverse");
     qfiles = (int)ini.count("Query") / 2;
 
@@ -52,6 +53,11 @@ int CoreRun::open(const std::string& ini_path) {
         // replay of a stored anchor / MUM list is outside the accelerated path; the driver never sets these keys
         std::cerr << "parsnp_core (MI355X build): anchorfile / mumfile are not supported by this build" << std::endl;
         return 1;
+    }
+
+    if (prm.snps && qfiles + 1 > snp_max_rows()) {      // (a limit of the engine, not a malfunction: its own exit code, before any work)
+        std::cerr << "parsnp_core: input exceeds a limit of the multi-MUM engine: snps=1 takes at most " << snp_max_rows() << " sequences" << std::endl;
+        return 5;
     }
 
     time_t start, end;

@@ -152,7 +152,7 @@ int main(int argc, char* argv[]) {
                     "\"gap_jobs\": %ld, \"gap_jobs_wide\": %ld, \"gap_longest\": %ld, \"gap_device_narrow\": %ld, \"gap_device_wide\": %ld, \"gap_host\": %ld, \"gap_host_s\": %.6f, "
                     "\"gap_device_narrow_ms\": %.3f, \"gap_device_wide_ms\": %.3f, \"gap_device_tall\": %ld, \"gap_device_tall_ms\": %.3f, "
                     "\"gap_jobs_long\": %ld, \"gap_device_long\": %ld, \"gap_device_long_ms\": %.3f, \"gap_device_long_tall\": %ld, \"gap_device_long_tall_ms\": %.3f, "
-                    "\"unalign_s\": %.6f, \"unalign_runs\": %ld, \"unalign_kept\": %ld, \"unalign_device_ms\": %.3f, \"unalign_d2h_bytes\": %.0f, \"session_d2h_bytes\": %.0f, \"layout_bytes\": %.0f}\n",
+                    "\"unalign_s\": %.6f, \"unalign_runs\": %ld, \"unalign_kept\": %ld, \"unalign_device_ms\": %.3f, \"unalign_d2h_bytes\": %.0f, \"session_d2h_bytes\": %.0f, \"layout_bytes\": %.0f",
                     pm_provider(), run.genomes.size(), run.qfiles, run.ingest_s, run.upload_s, rep.path_s, rep.anchor_s, rep.extend_s, rep.filter_s,
                     rep.lcb_s, output_s, now_s() - t_begin, rep.finder_s, rep.finder_calls, rep.finder_regions, rep.regions_processed,
                     rep.cache_hits, rep.cache_misses, rep.spec_rounds, rep.anchors, rep.mums, rep.lcbs, rep.core_bp, gap_note ? "true" : "false",
@@ -162,6 +162,10 @@ int main(int argc, char* argv[]) {
                     gap_counts.device_narrow_ms, gap_counts.device_wide_ms, gap_counts.device_tall, gap_counts.device_tall_ms,
                     gap_counts.jobs_long, gap_counts.device_long, gap_counts.device_long_ms, gap_counts.device_long_tall, gap_counts.device_long_tall_ms,
                     unalign_counts.s, unalign_counts.runs, unalign_counts.kept, unalign_counts.device_ms, unalign_counts.d2h_bytes, (double)session_d2h, layout_bytes);
+            if (snp_counts.on)      // (snps=1 only: without it the record has the keys it always had)
+                fprintf(f, ", \"snp_columns\": %ld, \"snp_core\": %ld, \"snp_other\": %ld, \"snp_h2d_bytes\": %.0f, \"snp_scan_ms\": %.3f, \"snp_dist_ms\": %.3f",
+                        snp_counts.columns, snp_counts.core, snp_counts.other, snp_counts.h2d_bytes, snp_counts.scan_ms, snp_counts.dist_ms);
+            fprintf(f, "}\n");
             fclose(f);
         }
     }

@@ -507,6 +507,13 @@ void write_output(Aligner& a, const std::string& stem, bool* gap_note) {
         if (note) notes[z] = 1;
     };
     vector<char> slow((size_t)nl, 0);
+    // snps=1 (snps.cpp): the columns between the MUMs go to the collector group after group, once the group is written.  A slow LCB
+    // keeps, from its finished rows (after the overlap trim), the columns that are not the same one of a c g t in every row.
+    snp_counts = SnpCounts();
+    std::unique_ptr<SnpCollector> snp;
+    if (prm.snps) snp.reset(new SnpCollector(a.session(), n, threads));
+    struct SlowSnp { long cols = 0; vector<int32_t> col; vector<int64_t> ref_left; vector<uint8_t> m; };      // m: n x col.size(), row-major
+    vector<SlowSnp> snp_slow(snp ? (size_t)nl : 0);
     for (long z = 0; z < nl; z++) if (printable_lcb(a.lcbs[(size_t)z]) && (all_slow || !plan[(size_t)z].regular)) slow[(size_t)z] = 1;
     auto stage_slow_rows = [&](size_t gz0, size_t gz1) {
         vector<long> which;
@@ -630,6 +637,22 @@ void write_output(Aligner& a, const std::string& stem, bool* gap_note) {
         }
         out += "=\n";
         bytes[z] = (long long)out.size();
+        if (snp) {
+            SlowSnp& sv = snp_slow[z];
+            sv.cols = (long)row[0].size();
+            auto at = [&](size_t i, size_t c) -> char { return c < row[i].size() ? row[i][c] : '-'; };
+            int64_t left = 0;
+            for (size_t c = 0; c < row[0].size(); c++) {
+                const char c0 = row[0][c];
+                bool mum = c0 == 'a' || c0 == 'c' || c0 == 'g' || c0 == 't';
+                for (size_t i = 1; i < n && mum; i++) mum = at(i, c) == c0;
+                if (!mum) { sv.col.push_back((int32_t)c); sv.ref_left.push_back(left); }
+                left += c0 != '-';
+            }
+            const size_t k = sv.col.size();
+            sv.m.resize(n * k);
+            for (size_t i = 0; i < n; i++) for (size_t x = 0; x < k; x++) sv.m[i * k + x] = (uint8_t)at(i, (size_t)sv.col[x]);
+        }
         vector<string>().swap(row);
     }
     };
@@ -775,6 +798,74 @@ void write_output(Aligner& a, const std::string& stem, bool* gap_note) {
         }
         if (bad) { cerr << "parsnp_core: error writing " << path << (bad == 2 ? " (record sizes)" : "") << endl; exit(1); }
     };
+    auto stage_snps = [&](size_t gz0, size_t gz1) {
+        if (!snp) return;
+        vector<int64_t> ref_pos;
+        for (size_t z = gz0; z < gz1; z++) {
+            if (!printed[z]) continue;
+            const Lcb& ct = trimmed[z];
+            const Mum& first = a.pool[(size_t)ct.mums.front()];
+            const int64_t ref_a = first.fwd[0] ? (int64_t)ct.start[0] + 1 : (int64_t)a.pool[(size_t)ct.mums.back()].start[0] + 1;      // the a of `> 1:a-b` (headers)
+            if (slow[z]) {
+                SlowSnp& sv = snp_slow[z];
+                const size_t k = sv.col.size();
+                snp->add_invariant(sv.cols - (long)k);
+                for (size_t p = 0; p < k;) {      // runs of consecutive columns, 4 096 at the most
+                    size_t q = p + 1;
+                    while (q < k && q - p < 4096 && sv.col[q] == sv.col[q - 1] + 1) q++;
+                    ref_pos.clear();
+                    for (size_t x = p; x < q; x++) ref_pos.push_back(ref_a + sv.ref_left[x]);
+                    snp->add_block((int)z + 1, sv.col[p], q - p, [&](size_t i, uint8_t* dst) { memcpy(dst, sv.m.data() + i * k + p, q - p); }, ref_pos.data(), 0);
+                    p = q;
+                }
+                SlowSnp().m.swap(sv.m);
+                continue;
+            }
+            // the gaps of a streamed LCB: listed, then filled by all threads (a thread takes rows, every block of them), as many
+            // blocks at a time as the staging matrix holds, then committed in order (the reference positions run from left to right)
+            const Lcb& c0 = a.lcbs[z];
+            const Plan& pl = plan[z];
+            struct Blk { size_t t; long col, gc; const Job* j; size_t at; };
+            vector<Blk> blks;
+            long col = 0;
+            for (size_t t = 0; t < c0.mums.size(); t++) {
+                const long len = a.pool[(size_t)c0.mums[t]].length;
+                snp->add_invariant(len); col += len;
+                if (t + 1 == c0.mums.size()) break;
+                const long gc = pl.gcols[t];
+                if (gc == 0) continue;
+                const Job* j = pl.gjob[t] >= 0 ? &jobs[(size_t)pl.gjob[t]] : nullptr;
+                size_t len0 = 0;
+                if (j && !aligned_row(*j, 0, &len0)) j = nullptr;      // (the alignment failed: padded, as it was written)
+                blks.push_back(Blk{t, col, gc, j, 0});
+                col += gc;
+            }
+            int64_t ref_left = 0; long last_col = 0;      // characters other than '-' of the reference row left of last_col
+            for (size_t b0 = 0; b0 < blks.size();) {
+                size_t b1 = b0, need = 0;
+                while (b1 < blks.size() && (b1 == b0 || need + (size_t)blks[b1].gc <= snp->pitch())) { blks[b1].at = need; need += (size_t)blks[b1].gc; b1++; }
+                uint8_t* base = snp->reserve(need);
+                const size_t pitch = snp->pitch();
+#pragma omp parallel for schedule(static) num_threads(threads)
+                for (long i = 0; i < (long)n; i++)
+                    for (size_t b = b0; b < b1; b++) {
+                        const Blk& k = blks[b];
+                        uint8_t* dst = base + (size_t)i * pitch + k.at;
+                        size_t w = 0;
+                        if (k.j) { const char* r = aligned_row(*k.j, (size_t)i, &w); memcpy(dst, r, w); }
+                        else w = gap_text(c0, k.t, (size_t)i, (char*)dst);
+                        memset(dst + w, '-', (size_t)k.gc - w);
+                    }
+                for (size_t b = b0; b < b1; b++) {
+                    const Blk& k = blks[b];
+                    ref_left += k.col - last_col;      // (the MUM columns in between hold no '-')
+                    ref_left += snp->commit((int)z + 1, k.col, (size_t)k.gc, nullptr, ref_a + ref_left);
+                    last_col = k.col + k.gc;
+                }
+                b0 = b1;
+            }
+        }
+    };
     // ---- group after group: wait for its alignments, lay it out, write it
     for (size_t g = 0; g < ngroups; g++) {
         const Group& G = batch[g];
@@ -795,6 +886,7 @@ void write_output(Aligner& a, const std::string& stem, bool* gap_note) {
         stage_in_order(G.z0, G.z1);
         stage_sizes(G.z0, G.z1);
         stage_write(G.z0, G.z1);
+        stage_snps(G.z0, G.z1);
         if (dbg) { char what[48]; snprintf(what, sizeof what, "group %zu written", g + 1); lap(what); }
     }
     device_side.get();
@@ -823,6 +915,7 @@ void write_output(Aligner& a, const std::string& stem, bool* gap_note) {
     }
 
     lap("xmfa records");
+    if (snp) { snp->finish(a.genomes, dir, stem); lap("snp columns"); }
     // ---- log (:1082-1190); stream flags are sticky exactly as in the reference
     log << "Number of sequences analyzed:" << setiosflags(ios::fixed) << setprecision(1) << setw(10) << n << endl << endl;
     for (size_t i = 0; i < n; i++) {

@@ -51,10 +51,13 @@ def driver_order(paths):
     return out
 
 
-def ini_text(ref, queries, outdir, **kw):
+def ini_text(ref, queries, outdir, snps=None, **kw):
+    """snps=1: `snps=1` under [Output] (core SNP columns and SNP distances beside the XMFA: read_snps; the reference ignores the
+    key).  Without the argument the text is the reference driver's, byte for byte."""
     p = dict(DEFAULTS, **kw)
     files = "".join("file%d=%s\nreverse%d=0\n" % (i, q, i) for i, q in enumerate(queries, 1))
-    return _TEMPLATE.format(ref=ref, files=files, outdir=outdir, **p)
+    text = _TEMPLATE.format(ref=ref, files=files, outdir=outdir, **p)
+    return text if snps is None else text + "snps=%d\n" % int(snps)
 
 
 def run_core(core_bin, ref, queries, outdir, timing=None, env=None, timeout=None, **kw):
@@ -81,3 +84,23 @@ def read_timing(path):
     import json
     with open(path) as f:
         return json.load(f)
+
+
+def read_snps(outdir, stem="parsnpAligner"):
+    """the three files a run with snps=1 leaves beside the XMFA -> (names, letters, rows, dist): the sequence names in header order,
+    letters uint8 [n, V] (the rows' letters in the core SNP columns, upper case), rows = [(cluster, column, ref_pos)] per core SNP
+    column, dist int32 [n, n] (the number of core SNP columns in which two sequences differ)"""
+    import numpy as np
+    base = os.path.join(outdir, stem)
+    lines = open(base + ".snps.mfa", "rb").read().split(b"\n")
+    assert lines[-1] == b"" and len(lines) % 2 == 1
+    names = [x[1:].decode() for x in lines[0:-1:2]]
+    assert all(x[:1] == b">" for x in lines[0:-1:2])
+    letters = np.array([np.frombuffer(x, np.uint8) for x in lines[1:-1:2]], np.uint8).reshape(len(names), -1)
+    tsv = open(base + ".snps.tsv").read().split("\n")
+    assert tsv[0] == "cluster\tcolumn\tref_pos" and tsv[-1] == ""
+    rows = [tuple(int(x) for x in line.split("\t")) for line in tsv[1:-1]]
+    dl = open(base + ".snps.dist").read().split("\n")
+    assert dl[-1] == "" and dl[0].split("\t") == [""] + names and [x.split("\t")[0] for x in dl[1:-1]] == names
+    dist = np.array([[int(x) for x in line.split("\t")[1:]] for line in dl[1:-1]], np.int32).reshape(len(names), len(names))
+    return names, letters, rows, dist
