@@ -282,7 +282,7 @@ private:
         size_t ev_guess = 0, slice_cap = 0, queue_cap = 0, grp_cap = 0;
         uint64_t nev = 0, nrest = 0, ngrp = 0, worst_slice = 0;
         uint32_t errbits = 0, sticky = 0;
-        bool first_form = false, wide_form = false, grouping = false, by_buckets = false, sharded = false;
+        bool first_form = false, wide_form = false, grouping = false, by_buckets = false, coarse_by_buckets = false, sharded = false;
         uint64_t *skey = nullptr, *sval = nullptr;      // the events in order
         // candidate tail: where the device keeps the candidate count; the call looks like an anchor call
         const int64_t* ncand_p = nullptr; bool anchor_guess = false;
@@ -491,6 +491,9 @@ private:
         ensure(d_repeated, (size_t)(npos / 32 + 2));       // (SeedExtend reads the word after a position's own)
         ensure(d_ucount, (size_t)npairs + 1); ensure(d_uoff, (size_t)npairs + 1);
         ensure(d_coarse, (size_t)std::max<int64_t>(centries, 1));
+        // (a call whose events go through the buckets writes every entry of the coarse index -- CoarseFromBuckets, zeros for the pairs
+        // without a bucketed event -- so the 16 MB of an anchor call are not cleared first; order_events clears them if no event came)
+        c.coarse_by_buckets = bucket_sort && (int64_t)c.nq * c.nchunks < ((int64_t)1 << 31);
         ensure(d_wmask, (size_t)nwv + 1); ensure(d_wcount, (size_t)nwv + 1); ensure(d_woff, (size_t)nwv + 1);
         if (from_store) ensure(d_alg, 8 * (size_t)kAlgSets);
         ensure(d_dense, regz);
@@ -498,7 +501,7 @@ private:
             // (the regions' dense flags as well -- but in the suffix-array run, which sets them from the host below)
             const ClearJob jobs[] = {
                 {d_filter.p, sizeof(uint32_t) * (size_t)fwords_clear, 0}, {d_slots.p, sizeof(uint64_t) * (size_t)tsize_clear, 0xff}, {d_counter.p, 8 * kCtrWords, 0},
-                {d_repeated.p, 4 * (size_t)(npos / 32 + 2), 0}, {d_coarse.p, 4 * (size_t)std::max<int64_t>(centries, 1), 0},
+                {d_repeated.p, 4 * (size_t)(npos / 32 + 2), 0}, {c.coarse_by_buckets ? nullptr : d_coarse.p, c.coarse_by_buckets ? 0 : 4 * (size_t)std::max<int64_t>(centries, 1), 0},
                 {d_ucount.p + npairs, 8, 0}, {d_wcount.p + nwv, 8, 0}, {from_store ? d_alg.p : nullptr, from_store ? (size_t)64 * kAlgSets : 0, 0},
                 {dense_mode ? nullptr : d_dense.p, dense_mode ? 0 : regz, 0}};
             be.clear_many(jobs, (int)(sizeof jobs / sizeof jobs[0]));
@@ -736,17 +739,20 @@ private:
         // (tune bucket_sort = 0: rounds 1-5) gathered, radix-sorted, and the table from a pass over the sorted keys
         const int64_t nbuckets = (int64_t)nq * nchunks;
         const bool by_buckets = c.by_buckets = bucket_sort && nev > 0 && nbuckets < ((int64_t)1 << 31);
+        if (c.coarse_by_buckets && !by_buckets) be.memset(d_coarse.p, 0, 4 * (size_t)std::max<int64_t>(centries, 1));      // (no bucketed event: nobody else writes the table's zeros)
         ensure(d_lo, (size_t)npairs + 1);
         if (by_buckets) {
-            ensure(d_bcount, (size_t)nbuckets + 1); ensure(d_bbegin, (size_t)nbuckets + 1); ensure(d_pbase, (size_t)npairs);
+            ensure(d_bcount, (size_t)nbuckets + 2); ensure(d_bbegin, (size_t)nbuckets + 2); ensure(d_pbase, (size_t)npairs);
             int shift = 6;
             while (((uint64_t)1 << shift) < worst_slice) shift++;      // (the fullest slice's count: known since the wait above)
-            be.memset(d_bcount.p, 0, 8 * ((size_t)nbuckets + 1));
+            // the counts one element up behind a 0: their scan is 0, begin[0 .. nbuckets] -- EventPlace's cursors from the second
+            // element on, and begin[] from the first once the events are placed (kernels.h)
+            be.memset(d_bcount.p, 0, 8 * ((size_t)nbuckets + 2));
             be.launch("pair_bucket_base", npairs, PairBucketBase{nq, d_cbase.p, d_pbase.p});
-            be.launch("event_bucket_count", (int64_t)kSlices << shift, EventBucketCount{d_evkey.p, d_counter.p, (uint64_t)slice_cap, shift, lbits, d_pbase.p, d_bcount.p});
-            be.exclusive_scan(d_bcount.p, d_bbegin.p, (size_t)nbuckets + 1);
+            be.launch("event_bucket_count", (int64_t)kSlices << shift, EventBucketCount{d_evkey.p, d_counter.p, (uint64_t)slice_cap, shift, lbits, d_pbase.p, d_bcount.p + 1});
+            be.exclusive_scan(d_bcount.p, d_bbegin.p, (size_t)nbuckets + 2);
             be.launch("event_place", (int64_t)kSlices << shift,
-                      EventPlace{d_evkey.p, d_evval.p, d_counter.p, (uint64_t)slice_cap, shift, lbits, d_pbase.p, d_bbegin.p, d_bcount.p, d_evkey3.p + ngrp, d_evval3.p + ngrp});
+                      EventPlace{d_evkey.p, d_evval.p, d_counter.p, (uint64_t)slice_cap, shift, lbits, d_pbase.p, d_bbegin.p + 1, d_evkey3.p + ngrp, d_evval3.p + ngrp});
             be.launch("event_order", nbuckets, EventOrder{d_bbegin.p, nbuckets, d_evkey3.p + ngrp, d_evval3.p + ngrp});
         } else if (nev > 0) {
             be.launch("compact_events", (int64_t)nev, CompactEvents{d_evkey.p, d_evval.p, d_sliceoff.p, (uint64_t)slice_cap, d_evkey2.p, d_evval2.p});
@@ -755,7 +761,7 @@ private:
         be.mark("scan");
         const int64_t nev_sorted = (int64_t)nev;
         nev += ngrp;
-        if (by_buckets) be.launch("coarse_from_buckets", centries, CoarseFromBuckets{d_bbegin.p, d_cbase.p, nreg, nq, (int64_t)ngrp, d_coarse.p, d_lo.p, npairs, nev_sorted});
+        if (by_buckets) be.launch_wave("coarse_from_buckets", coarse_tiles(centries / nq, nq), CoarseFromBuckets{d_bbegin.p, d_cbase.p, nreg, nq, (int64_t)ngrp, d_coarse.p, d_lo.p, npairs, nev_sorted, centries / nq});
         else be.launch("pair_bounds", npairs, PairBounds{skey, (int64_t)nev, lbits, npairs, d_lo.p, (int64_t)ngrp});
         if (grouping) be.launch("grouped_bounds", npairs, GroupedBounds{d_gflag.p, d_glo.p, nq, d_lo.p});
         // (the grouped events came with their states: the scan runs over the sorted part, its event numbers relative to it)
@@ -763,10 +769,11 @@ private:
         const int64_t nsorted = (int64_t)(nev - ngrp);
         if (nsorted > 0) {
             const int64_t nwaves = (nsorted + kWaveEvents - 1) / kWaveEvents;
-            ensure(d_wsummary, (size_t)nwaves);
+            ensure(d_wsummary, (size_t)nwaves); ensure(d_wcarry, (size_t)nwaves);
             const WaveScanCore core{skey + ngrp, sval + ngrp, nsorted, lbits, d_R.p, nq, d_rep.p};
             be.launch_wave("wave_summary", nwaves, WaveSummary{core, d_wsummary.p});
-            be.launch_wave("wave_scan", nwaves, WaveScan{core, d_wsummary.p, d_lo.p, (int64_t)ngrp, d_state.p + ngrp, d_emax.p + ngrp});
+            be.launch_wave("summary_carry", (nwaves + kCarryTiles - 1) / kCarryTiles, SummaryCarry{core, d_wsummary.p, nwaves, d_lo.p, (int64_t)ngrp, d_wcarry.p});
+            be.launch_wave("wave_scan", nwaves, WaveScan{core, d_wcarry.p, d_state.p + ngrp, d_emax.p + ngrp});
         }
 
         if (c.want_events) {   // parity hook (pm_find_events): sorted events + rep'
@@ -2071,10 +2078,10 @@ private:
     Buf<uint64_t> d_slots; Buf<uint32_t> d_filter, d_repeated; Buf<int32_t> d_next, d_rep, d_run, d_epm;
     Buf<int64_t> d_ucount, d_uoff; Buf<UnitRec> d_units;
     Buf<uint64_t> d_counter, d_evkey, d_evval, d_evkey2, d_evval2, d_evkey3, d_evval3; Buf<int64_t> d_sliceoff;
-    Buf<int64_t> d_lo, d_cov; Buf<EventAtK> d_state; Buf<PairState> d_wsummary; Buf<int32_t> d_emax;
+    Buf<int64_t> d_lo, d_cov; Buf<EventAtK> d_state; Buf<PairState> d_wsummary, d_wcarry; Buf<int32_t> d_emax;
     Buf<uint64_t> d_cand; Buf<GenomeAtK> d_at; Buf<uint8_t> d_ok; Buf<int32_t> d_ok_k, d_ok_lon, d_osp; Buf<uint8_t> d_ofwd;
     Buf<uint64_t> d_wmask; Buf<int64_t> d_wcount, d_woff;
-    Buf<int64_t> d_bcount, d_bbegin, d_pbase;      // the event buckets: counts, where each begins, every pair's first
+    Buf<int64_t> d_bcount, d_bbegin, d_pbase;      // the event buckets: counts (behind a 0), where each begins (EventPlace's cursors), every pair's first
     Buf<int64_t> d_okcnt, d_okpos, d_cbase; Buf<int32_t> d_coarse; Buf<int32_t> d_creg, d_ck, d_clon, d_csp; Buf<uint8_t> d_cfwd;
     Buf<uint32_t> d_cflags, d_dirty; Buf<int32_t> d_bmax, d_bmin;
     Buf<GenomeAtK> d_xsend, d_xrecv; Buf<uint8_t> d_hsend, d_hrecv;

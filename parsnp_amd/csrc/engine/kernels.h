@@ -1307,7 +1307,10 @@ struct CompactEvents {
 // form a BUCKET, the buckets numbered pair by pair, block by block.  So (round 6):
 //   EventBucketCount  one atomic add per event on its bucket's counter (the counters of a unit's events are neighbours);
 //   exclusive scan    over the 3.9 M counters: where every bucket begins in the final array;
-//   EventPlace        every event to its bucket (a second atomic gives it a place there), 16 bytes written once;
+//   EventPlace        every event to its bucket (a returning add on the bucket's cursor gives it a place there), 16 bytes written
+//                     once.  The scan leaves the cursors -- begin[] -- one element up in an array that starts with a 0: when every
+//                     event has its place, cursor[b] is where bucket b + 1 begins, and the array read from its first element is
+//                     begin[] again;
 //   EventOrder        a thread per bucket puts its few events in key order (insertion; a long bucket -- a degenerate repeat -- by
 //                     Shell's gaps);
 //   CoarseFromBuckets the block-major table of the readers and the pairs' bounds, from the scanned counters.
@@ -1349,7 +1352,7 @@ struct EventBucketCount {
 };
 struct EventPlace {
     const uint64_t* key_in; const uint64_t* val_in; const uint64_t* counters; uint64_t slice_cap; int shift; int lbits; const int64_t* pbase;
-    const int64_t* begin; int64_t* count; uint64_t* key_out; uint64_t* val_out;      // count: what EventBucketCount left (taken down to 0 here)
+    int64_t* cursor; uint64_t* key_out; uint64_t* val_out;      // cursor[b]: the next free place of bucket b -- where it begins, before; where bucket b + 1 begins, after
     PM_HD void operator()(int64_t tid) const {
         const uint64_t sl = (uint64_t)tid >> shift, idx = (uint64_t)tid & ((1ull << shift) - 1);
         const bool active = idx < counters[sl * kSliceStride];
@@ -1361,12 +1364,11 @@ struct EventPlace {
         const int64_t prev = ((int64_t)__shfl_up((int)(b >> 32), 1, 64) << 32) | (uint32_t)__shfl_up((int)(uint32_t)b, 1, 64);
         const bool head = active && (lane == 0 || prev != b);
         const unsigned long long heads = __ballot(head), act = __ballot(active);
-        int64_t first = 0;      // the run's first place (the places of a bucket are handed out from its end)
+        int64_t first = 0;      // the run's first place: one returning add per run and nothing else
         if (head) {
             const unsigned long long above = lane == 63 ? 0ull : heads & (~0ull << (lane + 1));
             const int upto = above ? __ffsll((long long)above) - 1 : __popcll(act);
-            const int64_t run = upto - lane;
-            first = begin[b] + (int64_t)atomic_add64((uint64_t*)&count[b], (uint64_t)(-run)) - run;
+            first = (int64_t)atomic_add64((uint64_t*)&cursor[b], (uint64_t)(upto - lane));
         }
         const unsigned long long below = heads & (lane == 63 ? ~0ull : ((2ull << lane) - 1));      // the heads at or before this lane
         const int mine = below ? 63 - __clzll((long long)below) : 0;
@@ -1377,8 +1379,7 @@ struct EventPlace {
 #else
         if (!active) return;
         const uint64_t k = key_in[src];
-        const int64_t b = bucket_of_key(k, lbits, pbase);
-        const int64_t at = begin[b] + (int64_t)atomic_add64((uint64_t*)&count[b], ~0ull) - 1;      // (the last free place of the bucket)
+        const int64_t at = (int64_t)atomic_add64((uint64_t*)&cursor[bucket_of_key(k, lbits, pbase)], 1);
         key_out[at] = k; val_out[at] = val_in[src];
 #endif
     }
@@ -1423,19 +1424,81 @@ struct EventOrder {
             }
     }
 };
-// tid = entry of the block-major table: (row of the batch, genome)
+// A wavefront per tile of the block-major table: kCoarseRows consecutive rows of the batch x kCoarseGen genomes.  The table wants a
+// row's genomes side by side, the buckets hold a genome's blocks side by side -- a transposition.  Where the tile's rows are one
+// region's, every genome's stretch of begin[] is read contiguously into LDS and the rows are written from there; a tile of
+// several regions (the recursion's, most of them one block) reads its entries directly, a row at a time -- its genomes' buckets
+// are neighbours or nearly so.  The region of a row is looked up once per row, by one lane.
+constexpr int kCoarseRows = 32, kCoarseGen = 64;
+PM_HD int64_t coarse_tiles(int64_t nrows, int32_t nq) { return ((nrows + kCoarseRows - 1) / kCoarseRows) * ((nq + kCoarseGen - 1) / kCoarseGen); }
 struct CoarseFromBuckets {
-    const int64_t* begin; const int64_t* cbase; int64_t nregions; int32_t nq; int64_t base; int32_t* coarse; int64_t* lo; int64_t npairs; int64_t total;
-    PM_HD void operator()(int64_t tid) const {
-        const int64_t row = tid / nq; const int64_t g = tid % nq;
+    const int64_t* begin; const int64_t* cbase; int64_t nregions; int32_t nq; int64_t base; int32_t* coarse; int64_t* lo; int64_t npairs; int64_t total; int64_t nrows;
+    PM_HD int64_t region_of_row(int64_t row) const {
         int64_t a = 0, z = nregions;
         while (z - a > 1) { const int64_t mid = (a + z) >> 1; if (cbase[mid] <= row) a = mid; else z = mid; }
-        const int64_t r = a, b = row - cbase[r], blocks = cbase[r + 1] - cbase[r] - 1;
-        const int64_t first = (int64_t)nq * (cbase[r] - r) + g * blocks;
-        const int64_t f = begin[first];
-        coarse[tid] = (int32_t)(begin[first + b] - f);      // (row `blocks`: the next pair's first bucket = the pair's count)
-        if (b == 0) lo[r * nq + g] = base + f;
-        if (tid == 0) lo[npairs] = base + total;
+        return a;
+    }
+    PM_HD void wave(int64_t w) const {
+        const int64_t gtiles = (nq + kCoarseGen - 1) / kCoarseGen;
+        const int64_t row0 = (w / gtiles) * kCoarseRows; const int32_t g0 = (int32_t)(w % gtiles) * kCoarseGen;
+        const int rows = (int)(nrows - row0 < kCoarseRows ? nrows - row0 : kCoarseRows), gens = nq - g0 < kCoarseGen ? nq - g0 : kCoarseGen;
+#if defined(__HIP_DEVICE_COMPILE__)
+        __shared__ int32_t s_v[kCoarseGen][kCoarseRows + 1];      // (+ 1: a row of the table is read across the genomes without bank conflicts)
+        __shared__ int64_t s_f[kCoarseGen];
+        __shared__ int64_t s_reg[kCoarseRows], s_cb[kCoarseRows], s_blocks[kCoarseRows];
+        const int lane = (int)__lane_id();
+        if (w == 0 && lane == 0) lo[npairs] = base + total;
+        if (lane < rows) {
+            const int64_t r = region_of_row(row0 + lane);
+            s_reg[lane] = r; s_cb[lane] = cbase[r]; s_blocks[lane] = cbase[r + 1] - cbase[r] - 1;
+        }
+        __syncthreads();
+        if (s_reg[0] == s_reg[rows - 1]) {      // one region: genome g's entries of these rows are begin[first_g + b0 ...], side by side
+            const int64_t r = s_reg[0], cb = s_cb[0], blocks = s_blocks[0], b0 = row0 - cb;
+            const int64_t pairs0 = (int64_t)nq * (cb - r);
+            if (lane < gens) {
+                const int64_t f = begin[pairs0 + (int64_t)(g0 + lane) * blocks];
+                s_f[lane] = f;
+                if (b0 == 0) lo[r * nq + g0 + lane] = base + f;
+            }
+            __syncthreads();
+            const int bl = lane & (kCoarseRows - 1);
+            for (int gl = lane / kCoarseRows; gl < gens; gl += 64 / kCoarseRows)
+                if (bl < rows) s_v[gl][bl] = (int32_t)(begin[pairs0 + (int64_t)(g0 + gl) * blocks + b0 + bl] - s_f[gl]);      // (row `blocks`: the next pair's first bucket = the pair's count)
+            __syncthreads();
+            if (lane < gens)
+                for (int x = 0; x < rows; x++) coarse[(row0 + x) * nq + g0 + lane] = s_v[lane][x];
+        } else if (lane < gens) {
+            constexpr int kAtOnce = 8;      // rows whose loads are under way together
+            for (int x0 = 0; x0 < rows; x0 += kAtOnce) {
+                int64_t f[kAtOnce]; int32_t v[kAtOnce];
+#pragma unroll
+                for (int t = 0; t < kAtOnce; t++) {
+                    const int x = x0 + t < rows ? x0 + t : rows - 1;
+                    const int64_t first = (int64_t)nq * (s_cb[x] - s_reg[x]) + (int64_t)(g0 + lane) * s_blocks[x];
+                    f[t] = begin[first]; v[t] = (int32_t)(begin[first + (row0 + x - s_cb[x])] - f[t]);
+                }
+#pragma unroll
+                for (int t = 0; t < kAtOnce; t++)
+                    if (x0 + t < rows) {
+                        const int x = x0 + t;
+                        coarse[(row0 + x) * nq + g0 + lane] = v[t];
+                        if (row0 + x == s_cb[x]) lo[s_reg[x] * nq + g0 + lane] = base + f[t];
+                    }
+            }
+        }
+#else
+        if (w == 0) lo[npairs] = base + total;
+        for (int x = 0; x < rows; x++) {
+            const int64_t row = row0 + x, r = region_of_row(row), b = row - cbase[r], blocks = cbase[r + 1] - cbase[r] - 1;
+            for (int32_t g = g0; g < g0 + gens; g++) {
+                const int64_t first = (int64_t)nq * (cbase[r] - r) + (int64_t)g * blocks;
+                const int64_t f = begin[first];
+                coarse[row * nq + g] = (int32_t)(begin[first + b] - f);
+                if (b == 0) lo[r * nq + g] = base + f;
+            }
+        }
+#endif
     }
 };
 
@@ -1467,8 +1530,8 @@ struct EventAtK { StrandAtK s[2]; };
 // per round (coalesced loads, 1.5 KB of states stored per instruction), six shuffle steps per round, the last lane's state
 // carried into the next round.  The state carries its winner's (l, j, rep') along, so the ties of equal reach are settled
 // without a load and the resolved record (EP, UP, SP - k) falls out of the registers.  A wavefront takes kWaveEvents consecutive
-// events; pass 1 leaves the state of every wavefront's trailing pair, pass 2 joins the summaries back to the wavefront its
-// first pair starts in (`lo`) and scans.  (Until round 4 a THREAD per 128 consecutive events: 64 lanes reading and writing 64
+// events; pass 1 leaves the state of every wavefront's trailing pair (a reduction: no scan), SummaryCarry makes of the summaries
+// the state that runs into every wavefront, pass 2 scans from there.  (Until round 4 a THREAD per 128 consecutive events: 64 lanes reading and writing 64
 // places 3 KB apart with every instruction, every step of a thread's loop a trip to memory, and a look back over up to 300
 // chunk summaries -- 0.55 ms for the anchor call's 7.7 M events against 0.28.)
 #ifndef PM_WAVE_EVENTS
@@ -1478,13 +1541,11 @@ constexpr int kWaveEvents = PM_WAVE_EVENTS;
 struct WinState { int32_t e1, e2, wl, wj, wr; };        // furthest end (0: no event), second furthest, the winner's l, j and rep'[l]
 struct PairState { WinState s[2]; };
 PM_HD WinState win_join(const WinState& a, const WinState& b) {      // a: earlier events, b: later events of the same pair and strand
-    if (a.e1 == 0) return b;
-    if (b.e1 == 0) return a;
-    const bool a_wins = a.e1 > b.e1 || (a.e1 == b.e1 && (a.wl < b.wl || (a.wl == b.wl && a.wj <= b.wj)));      // equal reach: the earlier (l, j)
-    WinState o;
-    if (a_wins) { o = a; o.e2 = a.e2 > b.e1 ? a.e2 : b.e1; }
-    else { o = b; o.e2 = b.e2 > a.e1 ? b.e2 : a.e1; }
-    return o;
+    // (selects, no branches: the lanes of a wavefront disagree about the winner all the time.  A side without events has e1 = 0 and
+    // loses to any event; its zeros change nothing in the winner's e2)
+    const bool a_wins = b.e1 == 0 || (a.e1 != 0 && (a.e1 > b.e1 || (a.e1 == b.e1 && (a.wl < b.wl || (a.wl == b.wl && a.wj <= b.wj)))));      // equal reach: the earlier (l, j)
+    const int32_t second = a_wins ? a.e2 : b.e2, loser = a_wins ? b.e1 : a.e1;
+    return WinState{a_wins ? a.e1 : b.e1, second > loser ? second : loser, a_wins ? a.wl : b.wl, a_wins ? a.wj : b.wj, a_wins ? a.wr : b.wr};
 }
 PM_HD PairState pair_join(const PairState& a, const PairState& b) { PairState o; o.s[0] = win_join(a.s[0], b.s[0]); o.s[1] = win_join(a.s[1], b.s[1]); return o; }
 PM_HD PairState pair_of_event(uint64_t k, uint64_t v, uint64_t lmask, int32_t rp) {
@@ -1517,77 +1578,146 @@ __device__ inline bool pair_scan(PairState& x, bool head) {
     }
     return h != 0;
 }
+// the join of every lane's state, in every lane (the join is associative and symmetric: a reduction)
+__device__ inline PairState pair_reduce(PairState x) {
+    for (int d = 32; d >= 1; d >>= 1) {
+        PairState y;
+        for (int sd = 0; sd < 2; sd++)
+            y.s[sd] = WinState{__shfl_xor(x.s[sd].e1, d, 64), __shfl_xor(x.s[sd].e2, d, 64), __shfl_xor(x.s[sd].wl, d, 64), __shfl_xor(x.s[sd].wj, d, 64), __shfl_xor(x.s[sd].wr, d, 64)};
+        x = pair_join(x, y);
+    }
+    return x;
+}
 #endif
-// what one wavefront does with its kWaveEvents events: `carry` = the state of its first pair before them (nothing if the
-// first event opens a pair); store = false: only the trailing pair's state comes back
+PM_HD PairState pair_none() { PairState o; o.s[0] = WinState{0, 0, 0, 0, 0}; o.s[1] = o.s[0]; return o; }
+// the region of a pair (pair / nq; a batch has fewer than 2^31 pairs -- plan_call -- and a 32-bit division is a fifth of the 64-bit one)
+PM_HD int64_t region_of_pair(uint64_t pair, int32_t nq) { return (int64_t)((uint32_t)pair / (uint32_t)nq); }
+constexpr int kCarryTiles = 16;      // wavefronts (of kWaveEvents events) whose carries one wavefront of SummaryCarry works out (its lanes 0 .. 15: the anchor
+                                     // call's 15 000 summaries are 950 wavefronts, a few per compute unit, where 64 per wavefront left most units without one)
+// what the scan's kernels share: the sorted events [0, nev) and what an event's repeat length is read through
 struct WaveScanCore {
     const uint64_t* key; const uint64_t* val; int64_t nev; int lbits; const RegionInfo* R; int32_t nq; const int32_t* rep;
-    PM_HD PairState run(int64_t w, PairState carry, bool store, EventAtK* st, int32_t* emax, bool* opened) const {
+    PM_HD uint64_t pair_at(int64_t i) const { return key[i] >> (lbits + 1); }
+    PM_HD int64_t end_of(int64_t w) const { return (w + 1) * kWaveEvents < nev ? (w + 1) * kWaveEvents : nev; }
+    // the host's form of both passes: the events of wavefront w one after the other; the state of its trailing pair comes back
+    PM_HD PairState sequential(int64_t w, PairState carry, bool store, EventAtK* st, int32_t* emax) const {
         const uint64_t lmask = (1ull << lbits) - 1;
-        const int64_t a = w * kWaveEvents, b = a + kWaveEvents < nev ? a + kWaveEvents : nev;
-        bool any_head = false;
-#if defined(__HIP_DEVICE_COMPILE__)
-        const int lane = (int)__lane_id();
-        for (int64_t base = a; base < b; base += 64) {
-            const int64_t i = base + lane;
-            const bool in = i < b;
-            PairState x; x.s[0] = WinState{0, 0, 0, 0, 0}; x.s[1] = x.s[0];
-            bool head = false;
-            if (in) {
-                const uint64_t k = key[i], v = val[i];
-                const uint64_t pair = k >> (lbits + 1);
-                head = i == 0 || (key[i - 1] >> (lbits + 1)) != pair;
-                x = pair_of_event(k, v, lmask, store ? rep[R[(int64_t)pair / nq].posbase + (int32_t)((k >> 1) & lmask)] : 0);
-            }
-            const bool h = pair_scan(x, head);
-            if (!h) x = pair_join(carry, x);                       // no pair opened at or before this lane: the carried pair goes on
-            if (in && store) { st[i] = resolved(x); emax[i] = x.s[0].e1 > x.s[1].e1 ? x.s[0].e1 : x.s[1].e1; }
-            const int last = (int)((b - base < 64 ? b - base : 64) - 1);
-            carry.s[0] = win_bcast(x.s[0], last); carry.s[1] = win_bcast(x.s[1], last);
-            any_head = any_head || __ballot(head) != 0;
-        }
-#else
+        const int64_t a = w * kWaveEvents, b = end_of(w);
         for (int64_t i = a; i < b; i++) {
             const uint64_t k = key[i], v = val[i];
             const uint64_t pair = k >> (lbits + 1);
-            const bool head = i == 0 || (key[i - 1] >> (lbits + 1)) != pair;
-            const PairState x = pair_of_event(k, v, lmask, store ? rep[R[(int64_t)pair / nq].posbase + (int32_t)((k >> 1) & lmask)] : 0);
+            const bool head = i == 0 || pair_at(i - 1) != pair;
+            const PairState x = pair_of_event(k, v, lmask, store ? rep[R[region_of_pair(pair, nq)].posbase + (int32_t)((k >> 1) & lmask)] : 0);
             carry = head ? x : pair_join(carry, x);
-            any_head = any_head || head;
             if (store) { st[i] = resolved(carry); emax[i] = carry.s[0].e1 > carry.s[1].e1 ? carry.s[0].e1 : carry.s[1].e1; }
         }
-#endif
-        if (opened) *opened = any_head;
         return carry;
     }
 };
-// pass 1, one wavefront per kWaveEvents events: the state of its trailing pair over its own events
+// pass 1, one wavefront per kWaveEvents events: the state of its trailing pair over its own events.  That pair is known from the
+// wavefront's last key, and its state is a reduction: every lane joins the events of the pair it meets (64 consecutive events per
+// load) into a state of its own, one butterfly joins the 64 states.
 struct WaveSummary {
     WaveScanCore core; PairState* summary;
     PM_HD void wave(int64_t w) const {
-        PairState none; none.s[0] = WinState{0, 0, 0, 0, 0}; none.s[1] = none.s[0];
-        PairState t = core.run(w, none, false, nullptr, nullptr, nullptr);
+        const int64_t a = w * kWaveEvents, b = core.end_of(w);
+        const uint64_t last = core.pair_at(b - 1);
+#if defined(__HIP_DEVICE_COMPILE__)
+        const uint64_t lmask = (1ull << core.lbits) - 1;
+        const int lane = (int)__lane_id();
+        PairState t = pair_none();
+        constexpr int rounds = (kWaveEvents + 63) / 64;
+        uint64_t k[rounds], v[rounds];
+#pragma unroll
+        for (int x = 0; x < rounds; x++) {       // (every load before the first join; past the end: the last event again, not joined)
+            const int64_t i = a + 64 * x + lane;
+            const int64_t at = i < b ? i : b - 1;
+            k[x] = core.key[at]; v[x] = core.val[at];
+        }
+#pragma unroll
+        for (int x = 0; x < rounds; x++)
+            if (a + 64 * x + lane < b && (k[x] >> (core.lbits + 1)) == last) t = pair_join(t, pair_of_event(k[x], v[x], lmask, 0));
+        t = pair_reduce(t);
+#else
+        PairState t = core.sequential(w, pair_none(), false, nullptr, nullptr);
+#endif
         if (wave_leader_k()) {      // (pass 1 runs without the repeat lengths -- they decide nothing -- and fetches the two winners' at the end)
-            const int64_t b = (w + 1) * kWaveEvents < core.nev ? (w + 1) * kWaveEvents : core.nev;
-            const int64_t posbase = core.R[(int64_t)(core.key[b - 1] >> (core.lbits + 1)) / core.nq].posbase;
+            const int64_t posbase = core.R[region_of_pair(last, core.nq)].posbase;
             if (t.s[0].e1) t.s[0].wr = core.rep[posbase + t.s[0].wl];
             if (t.s[1].e1) t.s[1].wr = core.rep[posbase + t.s[1].wl];
             summary[w] = t;
         }
     }
 };
-// pass 2: the carried state of the wavefront's first pair from the summaries of the wavefronts since that pair began, then the scan
-struct WaveScan {
-    WaveScanCore core; const PairState* summary; const int64_t* lo; int64_t lo_base; EventAtK* st; int32_t* emax;
-    PM_HD void wave(int64_t w) const {
-        PairState carry; carry.s[0] = WinState{0, 0, 0, 0, 0}; carry.s[1] = carry.s[0];
-        const int64_t a = w * kWaveEvents;
-        const uint64_t pair = core.key[a] >> (core.lbits + 1);
-        if (a > 0 && (core.key[a - 1] >> (core.lbits + 1)) == pair) {
-            const int64_t s0 = (lo[pair] - lo_base) / kWaveEvents;      // (the same in every lane: a loop of scalar loads)
-            for (int64_t p = s0; p < w; p++) carry = pair_join(carry, summary[p]);
+// between the passes: carry[w] = the state of wavefront w's first pair over the events before the wavefront (nothing if its first
+// event opens a pair) -- a segmented exclusive scan over the summaries.  A summary opens a segment when its wavefront holds the
+// first event of its trailing pair, which the keys on either side of the wavefront tell (the events are in pair order).  One
+// wavefront of this kernel takes kCarryTiles summaries, one per lane (the other lanes scan nothing); the state that runs into its first one is the join of the
+// summaries since that pair began (`lo`), taken 64 at a time and reduced -- pass 1 is complete by then: nobody waits for anybody.
+struct SummaryCarry {
+    WaveScanCore core; const PairState* summary; int64_t nwaves; const int64_t* lo; int64_t lo_base; PairState* carry;
+    PM_HD bool continues(int64_t w) const { return w > 0 && core.pair_at(w * kWaveEvents - 1) == core.pair_at(w * kWaveEvents); }      // wavefront w's first event goes on with the pair before it
+    PM_HD bool opens(int64_t w) const { return w == 0 || core.pair_at(w * kWaveEvents - 1) != core.pair_at(core.end_of(w) - 1); }   // wavefront w holds the first event of its trailing pair
+    PM_HD void wave(int64_t c) const {
+        const int64_t w0 = c * kCarryTiles;
+        const int64_t s0 = continues(w0) ? (lo[core.pair_at(w0 * kWaveEvents)] - lo_base) / kWaveEvents : w0;      // the wavefront that pair began in
+#if defined(__HIP_DEVICE_COMPILE__)
+        const int lane = (int)__lane_id();
+        PairState into = pair_none();
+        for (int64_t p = s0 + lane; p < w0; p += 64) into = pair_join(into, summary[p]);
+        if (s0 < w0) into = pair_reduce(into);
+        const int64_t w = w0 + lane;
+        const bool in = lane < kCarryTiles && w < nwaves;
+        PairState x = in ? summary[w] : pair_none();
+        const bool h = pair_scan(x, in && opens(w));
+        if (!h) x = pair_join(into, x);
+        PairState before;      // the inclusive state of the wavefront before this lane's
+        before.s[0] = win_shfl_up(x.s[0], 1); before.s[1] = win_shfl_up(x.s[1], 1);
+        if (lane == 0) before = into;
+        if (in) carry[w] = continues(w) ? before : pair_none();
+#else
+        PairState run = pair_none();
+        for (int64_t p = s0; p < w0; p++) run = pair_join(run, summary[p]);
+        for (int64_t w = w0; w < w0 + kCarryTiles && w < nwaves; w++) {
+            carry[w] = continues(w) ? run : pair_none();
+            run = opens(w) ? summary[w] : pair_join(run, summary[w]);
         }
-        (void)core.run(w, carry, true, st, emax, nullptr);
+#endif
+    }
+};
+// pass 2: the scan, a lane per event and 64 consecutive events per round (coalesced loads, 1.5 KB of states stored per instruction),
+// six shuffle steps per round, the last lane's state carried into the next round; the state before the wavefront's first event
+// comes from SummaryCarry.  (A run of eight consecutive events per lane and ONE wavefront scan per 512 events was measured: 317 us
+// for the anchor call against 168 -- every load and store instruction of a wavefront then touches 64 cache lines; it needs the
+// events and the records transposed through LDS.  profiles/event_scan.)
+struct WaveScan {
+    WaveScanCore core; const PairState* carry; EventAtK* st; int32_t* emax;
+    PM_HD void wave(int64_t w) const {
+#if defined(__HIP_DEVICE_COMPILE__)
+        const uint64_t lmask = (1ull << core.lbits) - 1;
+        const int lane = (int)__lane_id();
+        const int64_t a = w * kWaveEvents, b = core.end_of(w);
+        PairState into = carry[w];
+        for (int64_t base = a; base < b; base += 64) {
+            const int64_t i = base + lane;
+            const bool in = i < b;
+            PairState x = pair_none();
+            bool head = false;
+            if (in) {
+                const uint64_t k = core.key[i], v = core.val[i];
+                const uint64_t pair = k >> (core.lbits + 1);
+                head = i == 0 || core.pair_at(i - 1) != pair;
+                x = pair_of_event(k, v, lmask, core.rep[core.R[region_of_pair(pair, core.nq)].posbase + (int32_t)((k >> 1) & lmask)]);
+            }
+            const bool h = pair_scan(x, head);
+            if (!h) x = pair_join(into, x);                       // no pair opened at or before this lane: the carried pair goes on
+            if (in) { st[i] = resolved(x); emax[i] = x.s[0].e1 > x.s[1].e1 ? x.s[0].e1 : x.s[1].e1; }
+            const int last = (int)((b - base < 64 ? b - base : 64) - 1);
+            into.s[0] = win_bcast(x.s[0], last); into.s[1] = win_bcast(x.s[1], last);
+        }
+#else
+        (void)core.sequential(w, carry[w], true, st, emax);
+#endif
     }
 };
 
