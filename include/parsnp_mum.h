@@ -354,6 +354,19 @@ int pm_snp_begin(pm_session* s, int32_t n_rows);
 int pm_snp_add(pm_session* s, int64_t n_cols, int64_t pitch, const uint8_t* chars, pm_snp_counts* totals);
 int pm_snp_columns(pm_session* s, int64_t* col, uint8_t* letters);
 int pm_snp_distances(pm_session* s, int32_t* dist);
+/* Neighbour-joining tree over an n x n matrix of distances (3 <= n <= the limits call's 2 048, which needs no device): the caller's
+ * `dist` (row-major, symmetric, zero diagonal, no negative entry: checked on the host before the upload), or with dist == NULL the
+ * distances of the session's SNP collection, which must have been computed (pm_snp_distances) and have n rows; they are still on the
+ * device.  The tree is DEFINED in INTEGRATION.md 1b: IEEE double arithmetic, every operation rounded once in the order written, ties
+ * to the smallest (i, j).  joins: the n - 3 join records in order (slot i keeps the new node, slot j retires; dij, ri, rj are D[i][j],
+ * R[i], R[j] before the update; may be NULL for n == 3), last: the three slots left, ascending, and their distances.  Branch lengths
+ * and Newick are the caller's (host/tree.cpp): the device never divides.  All launches of a tree are queued without a host wait.
+ * PM_EINVAL: n < 3, a matrix that is not symmetric / has a non-zero diagonal / a negative entry, dist NULL without computed SNP
+ * distances or with another n.  PM_ELIMIT: n > 2 048.  Phase `nj` in pm_last_timing. */
+typedef struct pm_nj_join { int32_t i, j; double dij, ri, rj; } pm_nj_join;
+typedef struct pm_nj_last { int32_t a, b, c; double dab, dac, dbc; } pm_nj_last;
+int pm_nj_limits(int* max_rows);
+int pm_nj_tree(pm_session* s, int32_t n, const int32_t* dist, pm_nj_join* joins, pm_nj_last* last);
 /* bytes this session has moved over the host link so far (every copy the engine issued, both directions) */
 int pm_session_traffic(const pm_session* s, uint64_t* h2d_bytes, uint64_t* d2h_bytes);
 

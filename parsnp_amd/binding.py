@@ -81,6 +81,14 @@ class Lib:
         self._check(self.L.pm_snp_limits(C.byref(a)))
         return a.value
 
+    def nj_limits(self):
+        """rows a neighbour-joining tree takes (Session.nj_tree): pm_nj_limits"""
+        if not hasattr(self.L, "pm_nj_limits"):
+            raise PmError("this provider of the ABI has no pm_nj_limits")
+        a = C.c_int()
+        self._check(self.L.pm_nj_limits(C.byref(a)))
+        return a.value
+
     def _gap_limits_of(self, name):
         if not hasattr(self.L, name):
             raise PmError("this provider of the ABI has no %s" % name)
@@ -195,7 +203,30 @@ class Session:
         col, letters, dist = np.zeros(nv, np.int64), np.zeros((n, nv), np.uint8), np.zeros((n, n), np.int32)
         self.lib._check(L.pm_snp_columns(self.h, col.ctypes.data_as(v), letters.ctypes.data_as(v)))
         self.lib._check(L.pm_snp_distances(self.h, dist.ctypes.data_as(v)))
+        self._snp_rows = n
         return dict(zip(("columns", "core_invariant", "core_snps", "other"), (int(x) for x in totals))), col, letters, dist
+
+    NJ_JOIN = np.dtype([("i", np.int32), ("j", np.int32), ("dij", np.float64), ("ri", np.float64), ("rj", np.float64)])
+    NJ_LAST = np.dtype([("a", np.int32), ("b", np.int32), ("c", np.int32), ("pad", np.int32), ("dab", np.float64), ("dac", np.float64), ("dbc", np.float64)])
+
+    def nj_tree(self, dist=None, n=None):
+        """pm_nj_tree -> (joins, last): the neighbour-joining tree over dist, int32 [n, n], or with dist=None over
+        the distances of the last core_snps of this session (still on the device; n: its rows).  joins: a record array of n - 3
+        entries with the fields i, j (int32) and dij, ri, rj (float64); last: one record with a, b, c, dab, dac, dbc."""
+        L = self.lib.L
+        if not hasattr(L, "pm_nj_tree"):
+            raise PmError("this provider of the ABI has no pm_nj_tree")
+        v = C.c_void_p
+        L.pm_nj_tree.argtypes = [v, C.c_int32, v, v, v]
+        if dist is not None:
+            dist = np.ascontiguousarray(dist, np.int32)
+            assert dist.ndim == 2 and dist.shape[0] == dist.shape[1]
+            n = int(dist.shape[0])
+        elif n is None:
+            n = int(getattr(self, "_snp_rows", 3))
+        joins, last = np.zeros(max(n - 3, 0), self.NJ_JOIN), np.zeros(1, self.NJ_LAST)
+        self.lib._check(L.pm_nj_tree(self.h, n, dist.ctypes.data_as(v) if dist is not None else None, joins.ctypes.data_as(v), last.ctypes.data_as(v)))
+        return joins, last[0]
 
     def __enter__(self):
         return self

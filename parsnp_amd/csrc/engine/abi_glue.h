@@ -302,6 +302,16 @@ int pm_snp_distances(pm_session* s, int32_t* dist) {
     if (!s || !dist) return fail(PM_EINVAL, "bad argument");
     PM_STORE_CALL(s->engine->snp_distances(dist))
 }
+// neighbour-joining tree (nj_kernels.h)
+static_assert(sizeof(pm_nj_join) == sizeof(pm::NjJoinRec) && sizeof(pm_nj_join) == 32 && sizeof(pm_nj_last) == sizeof(pm::NjLastRec) && sizeof(pm_nj_last) == 40, "pm_nj records");
+int pm_nj_limits(int* max_rows) {
+    if (max_rows) *max_rows = pm::kNjMaxRows;
+    return PM_OK;
+}
+int pm_nj_tree(pm_session* s, int32_t n, const int32_t* dist, pm_nj_join* joins, pm_nj_last* last) {
+    if (!s || !last || (n > 3 && n <= pm::kNjMaxRows && !joins)) return fail(PM_EINVAL, "bad argument");
+    PM_STORE_CALL(s->engine->nj_tree(n, dist, (pm::NjJoinRec*)joins, (pm::NjLastRec*)last))
+}
 int pm_session_traffic(const pm_session* s, uint64_t* h2d_bytes, uint64_t* d2h_bytes) {
     if (!s) return PM_EINVAL;
     if (h2d_bytes) *h2d_bytes = s->backend->bytes_h2d;

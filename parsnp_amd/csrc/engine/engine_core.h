@@ -29,6 +29,7 @@
 #include "dense_kernels.h"
 #include "index_kernels.h"
 #include "snp_kernels.h"
+#include "nj_kernels.h"
 
 namespace pm {
 
@@ -1794,7 +1795,7 @@ public:
     int snp_begin(int32_t n_rows) {
         if (n_rows < 2) { error = "a SNP collection needs at least 2 rows"; return -2; }
         if (n_rows > kSnpMaxRows) { error = "a SNP collection takes at most " + std::to_string(kSnpMaxRows) + " rows"; return -5; }
-        snp_rows = n_rows; snp_cols = 0; snp_v = 0; snp_up_bytes = 0;
+        snp_rows = n_rows; snp_cols = 0; snp_v = 0; snp_up_bytes = 0; snp_dist_ready = false;
         ensure(d_snp_counts, 4);
         ClearJob job{d_snp_counts.p, 4 * sizeof(uint64_t), 0};
         be.clear_many(&job, 1);
@@ -1804,6 +1805,7 @@ public:
         if (snp_rows < 2) { error = "no SNP collection has been started"; return -2; }
         if (snp_cols + n_cols >= ((int64_t)1 << 31)) { error = "a SNP collection takes fewer than 2^31 columns"; return -5; }
         timing.clear();
+        snp_dist_ready = false;
         const size_t n = (size_t)snp_rows, nc = (size_t)n_cols;
         uint64_t counts[4] = {0, 0, 0, 0};
         if (n_cols) {
@@ -1864,9 +1866,10 @@ public:
     int snp_distances(int32_t* dist) {
         if (snp_rows < 2) { error = "no SNP collection has been started"; return -2; }
         const size_t n = (size_t)snp_rows;
-        if (!snp_v) { memset(dist, 0, 4 * n * n); return 0; }
+        if (!snp_v) { memset(dist, 0, 4 * n * n); snp_dist_ready = true; return 0; }
         timing.clear();
         ensure(d_snp_dist, n * n);
+        snp_dist_ready = true;
         const int32_t tiles = (snp_rows + kSnpTile - 1) / kSnpTile;
         const int64_t words = (snp_v + 63) / 64;
         const uint64_t last_mask = (snp_v & 63) ? ((1ull << (snp_v & 63)) - 1) : ~0ull;
@@ -1878,6 +1881,57 @@ public:
         return 0;
     }
     int32_t snp_rows = 0; int64_t snp_cols = 0, snp_v = 0; uint64_t snp_up_bytes = 0;
+    bool snp_dist_ready = false;      // the collection's distances have been computed (nj_tree may take them from the device)
+
+    // Neighbour joining (nj_kernels.h) over a caller's matrix or over the distances of the session's SNP collection,
+    // which are still on the device.  The number of joins is known: all 2 (n - 3) + 2 launches are queued without a wait, and the
+    // records come back in one download.  joins: n - 3 records (may be null for n == 3), last: one.
+    int nj_tree(int32_t n, const int32_t* dist, NjJoinRec* joins, NjLastRec* last) {
+        if (n < 3) { error = "a neighbour-joining tree needs at least 3 rows"; return -2; }
+        if (n > kNjMaxRows) { error = "a neighbour-joining tree takes at most " + std::to_string(kNjMaxRows) + " rows"; return -5; }
+        const size_t N = (size_t)n;
+        if (!dist) {
+            if (!snp_dist_ready || snp_rows != n) { error = "no SNP distances of " + std::to_string(n) + " rows have been computed in this session"; return -2; }
+        } else {
+            for (size_t i = 0; i < N; i++) {
+                if (dist[i * N + i] != 0) { error = "the distance matrix has a non-zero diagonal"; return -2; }
+                for (size_t j = i + 1; j < N; j++) {
+                    if (dist[i * N + j] < 0) { error = "the distance matrix has a negative entry"; return -2; }
+                    if (dist[i * N + j] != dist[j * N + i]) { error = "the distance matrix is not symmetric"; return -2; }
+                }
+            }
+        }
+        timing.clear();
+        ensure(d_nj_D, N * N); ensure(d_nj_R, N); ensure(d_nj_active, N); ensure(d_nj_q, N); ensure(d_nj_j, N);
+        ensure(d_nj_joins, N); ensure(d_nj_last, 1);
+        const int32_t* src;
+        if (dist) {
+            ensure(d_nj_dist, N * N);
+            be.h2d(d_nj_dist.p, dist, 4 * N * N);
+            src = d_nj_dist.p;
+        } else {
+            if (!snp_v) {      // no core SNP: the distances call wrote zeros to the caller and launched nothing
+                ensure(d_snp_dist, N * N);
+                ClearJob job{d_snp_dist.p, 4 * N * N, 0};
+                be.clear_many(&job, 1);
+            }
+            src = d_snp_dist.p;
+        }
+        be.mark("nj");
+        be.launch_wave("nj_init", n, NjInit{src, n, d_nj_D.p, d_nj_R.p, d_nj_active.p});
+        for (int32_t t = 0; t + 3 < n; t++) {
+            const int32_t r = n - t;
+            be.launch_wave("nj_rowmin", n, NjRowMin{d_nj_D.p, d_nj_R.p, d_nj_active.p, n, r, d_nj_q.p, d_nj_j.p});
+            be.launch("nj_join", kNjGroup, NjJoin{d_nj_D.p, d_nj_R.p, d_nj_active.p, n, r, d_nj_q.p, d_nj_j.p, d_nj_joins.p + t});
+        }
+        be.launch_wave("nj_last", 1, NjLast{d_nj_D.p, d_nj_active.p, n, d_nj_last.p});
+        be.mark(nullptr);
+        if (n > 3 && joins) be.d2h_async(joins, d_nj_joins.p, (N - 3) * sizeof(NjJoinRec));
+        be.d2h_async(last, d_nj_last.p, sizeof(NjLastRec));
+        be.sync();
+        collect_timing_more();
+        return 0;
+    }
 
     // The suffix array of the flagged regions of a batch (dense_kernels.h) and their rep' (after RepeatLength, which skipped them).
     // One segmented prefix-doubling sort over all of them; every round waits for its count of distinct ranks (8 bytes) -- a round
@@ -2094,6 +2148,7 @@ private:
     int64_t table_counter = 0;
     Buf<uint64_t> d_image;
     Buf<int64_t> d_un_blk, d_un_cnt, d_un_scan, d_un_tot; Buf<int32_t> d_un_out;      // the unaligned runs: block geometry, counts per block, their scans, totals per genome, the runs
+    Buf<double> d_nj_D, d_nj_R, d_nj_q; Buf<uint8_t> d_nj_active; Buf<int32_t> d_nj_j, d_nj_dist; Buf<NjJoinRec> d_nj_joins; Buf<NjLastRec> d_nj_last;      // a neighbour-joining tree (nj_kernels.h)
     Buf<uint64_t> d_snp_counts, d_snp_lo, d_snp_hi; Buf<uint8_t> d_snp_chunk; Buf<int64_t> d_snp_flag, d_snp_rank, d_snp_col; Buf<int32_t> d_snp_dist;      // the SNP collection (snp_kernels.h)
     Buf<uint8_t> d_ms_strand, d_ms_state, d_small8, d_o_strand; Buf<int32_t> d_ms_shift, d_ms_len, d_list, d_list2, d_j_min, d_j_max, d_o_start;
     Buf<int64_t> d_rg_start, d_rg_len, d_lay_off, d_lay_bits, d_v_row0, d_v_first, d_f_start, d_f_end, d_f_pack; Buf<RegInfo> d_rg_info; Buf<uint64_t> d_rg_count, d_once, d_twice;

@@ -49,6 +49,7 @@ struct Params {
     int c = 0, d = 0, q = 0, p = 0, do_align = 0, cores = 2, random = 0;
     bool unaligned = false, recomb_filter = false, anchors_only = false, calc_mumi = false, extend_mums = false;
     bool snps = false;      // [Output] snps: core SNP columns and SNP distances beside the XMFA (snps.cpp); the reference ignores the key
+    bool tree = false;      // [Output] tree: the neighbour-joining tree of the SNP distances beside them (tree.cpp); implies snps
     float diag_diff = 1.0f, factor = 0.0f;
     std::string anchors, mums, anchorfile, mumfile, prefix, outdir;
 };
@@ -529,7 +530,8 @@ public:
     uint8_t* reserve(size_t width);
     long commit(int cluster, long c0, size_t width, const int64_t* ref_pos, int64_t ref_base);
     // the three files beside the XMFA, the console line, snp_counts
-    void finish(const std::vector<Genome>& genomes, const std::string& dir, const std::string& stem);
+    // (tree: then the neighbour-joining tree of the distances, which are still on the device -- tree.cpp)
+    void finish(const std::vector<Genome>& genomes, const std::string& dir, const std::string& stem, bool tree = false);
 
 private:
     struct Entry { int64_t first; int32_t cluster; int32_t width; int64_t c0; };      // columns [first, first + width) of all columns handed over
@@ -541,6 +543,16 @@ private:
     pm_snp_counts counts_{0, 0, 0, 0};
     double scan_ms_ = 0, h2d_bytes_ = 0;
 };
+
+// The neighbour-joining tree of the SNP distances ([Output] tree=1; tree.cpp): the engine joins (pm_nj_tree over the
+// distances the session has just computed), the host turns the join records into branch lengths and one line of Newick.
+struct TreeCounts { bool on = false; double nj_ms = 0; long joins = 0; };
+extern TreeCounts tree_counts;      // what the last write_output built (PARSNP_TIMING: nj_*, with tree=1 only)
+int tree_max_rows();                // sequences a run with tree=1 may have
+// the Newick line (without the newline) of n >= 3 names from the engine's records
+std::string nj_newick(const std::vector<std::string>& names, const pm_nj_join* joins, const pm_nj_last& last);
+// <stem>.snps.nwk; dist: the n x n distances on the host (read for n == 2 only: the engine is not called then)
+void write_tree(pm_session* session, const std::vector<std::string>& names, const int32_t* dist, const std::string& dir, const std::string& stem);
 
 std::string reverse_complement(const std::string& s);   // Aligner::reversec, :1294-1393
 

@@ -46,6 +46,8 @@ int CoreRun::open(const std::string& ini_path) {
     prm.prefix = ini.get("Output", "prefix", "parsnp");
     prm.outdir = ini.get("Output", "outdir", "output");
     prm.snps = ini.get_bool("Output", "snps");
+    prm.tree = ini.get_bool("Output", "tree");
+    if (prm.tree) prm.snps = true;      // (the tree is built over the SNP distances)
     const bool reverse_ref = ini.get_bool("Reference", "reverse");
     qfiles = (int)ini.count("Query") / 2;
 
@@ -57,6 +59,10 @@ int CoreRun::open(const std::string& ini_path) {
 
     if (prm.snps && qfiles + 1 > snp_max_rows()) {      // (a limit of the engine, not a malfunction: its own exit code, before any work)
         std::cerr << "parsnp_core: input exceeds a limit of the multi-MUM engine: snps=1 takes at most " << snp_max_rows() << " sequences" << std::endl;
+        return 5;
+    }
+    if (prm.tree && qfiles + 1 > tree_max_rows()) {
+        std::cerr << "parsnp_core: input exceeds a limit of the multi-MUM engine: tree=1 takes at most " << tree_max_rows() << " sequences" << std::endl;
         return 5;
     }
 

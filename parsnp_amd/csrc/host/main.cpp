@@ -165,6 +165,8 @@ int main(int argc, char* argv[]) {
             if (snp_counts.on)      // (snps=1 only: without it the record has the keys it always had)
                 fprintf(f, ", \"snp_columns\": %ld, \"snp_core\": %ld, \"snp_other\": %ld, \"snp_h2d_bytes\": %.0f, \"snp_scan_ms\": %.3f, \"snp_dist_ms\": %.3f",
                         snp_counts.columns, snp_counts.core, snp_counts.other, snp_counts.h2d_bytes, snp_counts.scan_ms, snp_counts.dist_ms);
+            if (tree_counts.on)      // (tree=1 only)
+                fprintf(f, ", \"nj_ms\": %.3f, \"nj_joins\": %ld", tree_counts.nj_ms, tree_counts.joins);
             fprintf(f, "}\n");
             fclose(f);
         }

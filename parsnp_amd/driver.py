@@ -51,13 +51,18 @@ def driver_order(paths):
     return out
 
 
-def ini_text(ref, queries, outdir, snps=None, **kw):
+def ini_text(ref, queries, outdir, snps=None, tree=None, **kw):
     """snps=1: `snps=1` under [Output] (core SNP columns and SNP distances beside the XMFA: read_snps; the reference ignores the
-    key).  Without the argument the text is the reference driver's, byte for byte."""
+    key).  tree=1: `tree=1` there (it implies snps=1: the neighbour-joining tree of the SNP distances, read_tree).  Without the
+    arguments the text is the reference driver's, byte for byte."""
     p = dict(DEFAULTS, **kw)
     files = "".join("file%d=%s\nreverse%d=0\n" % (i, q, i) for i, q in enumerate(queries, 1))
     text = _TEMPLATE.format(ref=ref, files=files, outdir=outdir, **p)
-    return text if snps is None else text + "snps=%d\n" % int(snps)
+    if snps is not None:
+        text += "snps=%d\n" % int(snps)
+    if tree is not None:
+        text += "tree=%d\n" % int(tree)
+    return text
 
 
 def run_core(core_bin, ref, queries, outdir, timing=None, env=None, timeout=None, **kw):
@@ -104,3 +109,10 @@ def read_snps(outdir, stem="parsnpAligner"):
     assert dl[-1] == "" and dl[0].split("\t") == [""] + names and [x.split("\t")[0] for x in dl[1:-1]] == names
     dist = np.array([[int(x) for x in line.split("\t")[1:]] for line in dl[1:-1]], np.int32).reshape(len(names), len(names))
     return names, letters, rows, dist
+
+
+def read_tree(outdir, stem="parsnpAligner"):
+    """the Newick string a run with tree=1 leaves beside the SNP files (one line: the file without its newline)"""
+    text = open(os.path.join(outdir, stem + ".snps.nwk")).read()
+    assert text.endswith(";\n") and text.count("\n") == 1
+    return text[:-1]
