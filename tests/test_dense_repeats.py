@@ -1,8 +1,9 @@
 """The suffix-array path of the event search (parsnp_amd/csrc/engine/dense_kernels.h) in the kernel emulation, against the CPU
 restatement: regions whose K-mer chain walks exhaust the per-thread work budget -- tandem repeats of period > 1 with hundreds of
 copies -- are flagged and run again on the suffix array instead of failing with PM_ELIMIT; tune "dense_all" puts every region
-on it.  rep' of the path is checked through the candidates (every event test compares ms with rep'[l0]); pm_find_events runs
-a session of its own with the default tunables, so it cannot select the path."""
+on it.  rep' of the path is checked here through the candidates (every event test compares ms with rep'[l0]).  pm_find_events runs
+a session of its own, which PARSNP_TUNE=dense_all=1 puts on the path: tests/test_dense_edges.py compares rep' and the events of
+SeedDense one by one that way."""
 import ctypes as C
 import os
 
