@@ -367,6 +367,32 @@ typedef struct pm_nj_join { int32_t i, j; double dij, ri, rj; } pm_nj_join;
 typedef struct pm_nj_last { int32_t a, b, c; double dab, dac, dbc; } pm_nj_last;
 int pm_nj_limits(int* max_rows);
 int pm_nj_tree(pm_session* s, int32_t n, const int32_t* dist, pm_nj_join* joins, pm_nj_last* last);
+/* Bootstrap support of the neighbour-joining tree of the session's SNP collection (DEFINED in INTEGRATION.md 1c; exact, like 1a and
+ * 1b).  The limits call reports the rows (2 048), the replicates of a call (1 024) and the largest column weight (15); it needs no
+ * device.
+ * pm_boot_distances: `reps` weighted distance matrices over the collection's core SNP columns (its own distances need not have been
+ * computed).  weights == NULL: replicate b draws V columns with replacement from `seed` (the draws of 1c) and a column's weight is
+ * the number of draws that picked it, capped at 15.  Otherwise weights is uint8 [reps][V] with row pitch `pitch`.  weights_out
+ * (uint8 [reps][V], packed) and dist_out (int32 [reps][n][n]) may be NULL; the distances stay on the device for pm_nj_trees.
+ * PM_EINVAL: no collection started, reps < 1, pitch < V, a weight above 15 (checked on the host before the upload).  PM_ELIMIT:
+ * reps > 1 024, or the draw counters of ONE replicate do not fit the batch's budget.  Phases `boot_draw` and `boot_dist`.
+ * pm_nj_trees: `count` trees of one n (3 <= n <= 2 048), each the tree of pm_nj_tree bit for bit, the trees of a batch joined in lock
+ * step: 2 (n - 3) + 2 launches a batch and no host wait.  dist: the caller's int32 [count][n][n], every matrix checked like
+ * pm_nj_tree's; NULL: the first `count` replicate distances on the device.  joins is [count][n - 3] and last is [count]; either may be
+ * NULL; the records stay on the device for pm_nj_support.  PM_EINVAL: n < 3, count < 1, a bad matrix, dist NULL without replicate
+ * distances of n rows and at least count replicates.  PM_ELIMIT: n > 2 048, count > 1 024.  Phase `boot_nj`.
+ * pm_nj_support: support[t] (int32 [n - 3]) = the number of the `count` trees one of whose n - 3 splits equals, as a set of leaves,
+ * the split of join t of main_joins (the node of a join holds the leaves of both slots joined; its split is that set, or the
+ * complement when leaf 0 is in it).  rep_joins: the caller's [count][n - 3] records, or NULL for the device's (the last
+ * pm_nj_trees of this n with at least count trees).  n == 3: nothing to count, nothing is written.  PM_EINVAL: n < 3, count < 1, a
+ * caller's record that does not have 0 <= i < j < n with both slots still active, rep_joins NULL without such records on the
+ * device.  PM_ELIMIT: n > 2 048, count > 1 024.  Phase `boot_support`.
+ * Replicates are worked off in batches (a batch's draw counters within 256 MiB, its trees' matrices within 1 GiB);
+ * pm_session_tune(s, "boot_batch", k) forces k a batch (0: the default); no result depends on k. */
+int pm_boot_limits(int* max_rows, int* max_reps, int* max_weight);
+int pm_boot_distances(pm_session* s, int32_t reps, uint64_t seed, const uint8_t* weights, int64_t pitch, uint8_t* weights_out, int32_t* dist_out);
+int pm_nj_trees(pm_session* s, int32_t n, int32_t count, const int32_t* dist, pm_nj_join* joins, pm_nj_last* last);
+int pm_nj_support(pm_session* s, int32_t n, const pm_nj_join* main_joins, int32_t count, const pm_nj_join* rep_joins, int32_t* support);
 /* bytes this session has moved over the host link so far (every copy the engine issued, both directions) */
 int pm_session_traffic(const pm_session* s, uint64_t* h2d_bytes, uint64_t* d2h_bytes);
 

@@ -89,6 +89,11 @@ class Lib:
         self._check(self.L.pm_nj_limits(C.byref(a)))
         return a.value
 
+    def boot_limits(self):
+        """(rows, replicates of a call, largest column weight) of the bootstrap (Session.boot_distances, nj_trees, nj_support):
+        pm_boot_limits"""
+        return self._gap_limits_of("pm_boot_limits")
+
     def _gap_limits_of(self, name):
         if not hasattr(self.L, name):
             raise PmError("this provider of the ABI has no %s" % name)
@@ -203,7 +208,7 @@ class Session:
         col, letters, dist = np.zeros(nv, np.int64), np.zeros((n, nv), np.uint8), np.zeros((n, n), np.int32)
         self.lib._check(L.pm_snp_columns(self.h, col.ctypes.data_as(v), letters.ctypes.data_as(v)))
         self.lib._check(L.pm_snp_distances(self.h, dist.ctypes.data_as(v)))
-        self._snp_rows = n
+        self._snp_rows, self._snp_core = n, nv
         return dict(zip(("columns", "core_invariant", "core_snps", "other"), (int(x) for x in totals))), col, letters, dist
 
     NJ_JOIN = np.dtype([("i", np.int32), ("j", np.int32), ("dij", np.float64), ("ri", np.float64), ("rj", np.float64)])
@@ -227,6 +232,72 @@ class Session:
         joins, last = np.zeros(max(n - 3, 0), self.NJ_JOIN), np.zeros(1, self.NJ_LAST)
         self.lib._check(L.pm_nj_tree(self.h, n, dist.ctypes.data_as(v) if dist is not None else None, joins.ctypes.data_as(v), last.ctypes.data_as(v)))
         return joins, last[0]
+
+    def boot_distances(self, reps, seed=1, weights=None):
+        """pm_boot_distances -> (weights, dist): the weighted SNP distances of `reps` bootstrap replicates over the
+        core SNP columns of the last core_snps of this session.  weights=None: the columns are drawn from `seed`; otherwise uint8
+        [reps, V], every value at most 15 (a view with a larger row stride is handed over as it lies).  weights: uint8 [reps, V] as
+        used; dist: int32 [reps, n, n].  The distances stay on the device for nj_trees()."""
+        L = self.lib.L
+        if not hasattr(L, "pm_boot_distances"):
+            raise PmError("this provider of the ABI has no pm_boot_distances")
+        v = C.c_void_p
+        L.pm_boot_distances.argtypes = [v, C.c_int32, C.c_uint64, v, C.c_int64, v, v]
+        n, nv = int(getattr(self, "_snp_rows", 0)), int(getattr(self, "_snp_core", 0))
+        given, pitch = None, 0
+        if weights is not None:
+            weights = np.asarray(weights)
+            assert weights.dtype == np.uint8 and weights.shape == (reps, nv)
+            if nv and not (weights.strides[1] == 1 and weights.strides[0] >= nv):
+                weights = np.ascontiguousarray(weights)
+            given, pitch = weights.ctypes.data_as(v), int(weights.strides[0]) if nv else 0
+        wout, dist = np.zeros((max(reps, 0), nv), np.uint8), np.zeros((max(reps, 0), n, n), np.int32)
+        self.lib._check(L.pm_boot_distances(self.h, reps, seed & (2 ** 64 - 1), given, pitch, wout.ctypes.data_as(v), dist.ctypes.data_as(v)))
+        self._boot_reps = reps
+        return wout, dist
+
+    def nj_trees(self, dist=None, n=None, count=None):
+        """pm_nj_trees -> (joins, last): `count` neighbour-joining trees of one n, each the tree of nj_tree() bit for bit, joined in
+        lock step.  dist: int32 [count, n, n], or None for the replicate distances of the last boot_distances (n: its rows, count:
+        its replicates).  joins: record array [count, n - 3]; last: record array [count].  The records stay on the device for
+        nj_support()."""
+        L = self.lib.L
+        if not hasattr(L, "pm_nj_trees"):
+            raise PmError("this provider of the ABI has no pm_nj_trees")
+        v = C.c_void_p
+        L.pm_nj_trees.argtypes = [v, C.c_int32, C.c_int32, v, v, v]
+        if dist is not None:
+            dist = np.ascontiguousarray(dist, np.int32)
+            assert dist.ndim == 3 and dist.shape[1] == dist.shape[2]
+            count, n = int(dist.shape[0]), int(dist.shape[1])
+        else:
+            n = int(getattr(self, "_snp_rows", 3)) if n is None else n
+            count = int(getattr(self, "_boot_reps", 1)) if count is None else count
+        joins, last = np.zeros((max(count, 0), max(n - 3, 0)), self.NJ_JOIN), np.zeros(max(count, 0), self.NJ_LAST)
+        self.lib._check(L.pm_nj_trees(self.h, n, count, dist.ctypes.data_as(v) if dist is not None else None, joins.ctypes.data_as(v), last.ctypes.data_as(v)))
+        self._boot_trees = count
+        return joins, last
+
+    def nj_support(self, n, main_joins, rep_joins=None, count=None):
+        """pm_nj_support -> support, int32 [n - 3]: in how many of `count` trees the split of every join of main_joins occurs, as a set
+        of leaves.  rep_joins: record array [count, n - 3], or None for the records of the last nj_trees() on the device."""
+        L = self.lib.L
+        if not hasattr(L, "pm_nj_support"):
+            raise PmError("this provider of the ABI has no pm_nj_support")
+        v = C.c_void_p
+        L.pm_nj_support.argtypes = [v, C.c_int32, v, C.c_int32, v, v]
+        main_joins = np.ascontiguousarray(main_joins, self.NJ_JOIN)
+        assert main_joins.shape == (max(n - 3, 0),)
+        if rep_joins is not None:
+            rep_joins = np.ascontiguousarray(rep_joins, self.NJ_JOIN)
+            assert rep_joins.ndim == 2 and rep_joins.shape[1] == max(n - 3, 0)
+            count = int(rep_joins.shape[0])
+        elif count is None:
+            count = int(getattr(self, "_boot_trees", 1))
+        support = np.zeros(max(n - 3, 0), np.int32)
+        self.lib._check(L.pm_nj_support(self.h, n, main_joins.ctypes.data_as(v), count, rep_joins.ctypes.data_as(v) if rep_joins is not None else None,
+                                        support.ctypes.data_as(v)))
+        return support
 
     def __enter__(self):
         return self

@@ -312,6 +312,25 @@ int pm_nj_tree(pm_session* s, int32_t n, const int32_t* dist, pm_nj_join* joins,
     if (!s || !last || (n > 3 && n <= pm::kNjMaxRows && !joins)) return fail(PM_EINVAL, "bad argument");
     PM_STORE_CALL(s->engine->nj_tree(n, dist, (pm::NjJoinRec*)joins, (pm::NjLastRec*)last))
 }
+// bootstrap support of the SNP tree (boot_kernels.h)
+int pm_boot_limits(int* max_rows, int* max_reps, int* max_weight) {
+    if (max_rows) *max_rows = pm::kNjMaxRows;
+    if (max_reps) *max_reps = pm::kBootMaxReps;
+    if (max_weight) *max_weight = pm::kBootMaxWeight;
+    return PM_OK;
+}
+int pm_boot_distances(pm_session* s, int32_t reps, uint64_t seed, const uint8_t* weights, int64_t pitch, uint8_t* weights_out, int32_t* dist_out) {
+    if (!s) return fail(PM_EINVAL, "bad argument");
+    PM_STORE_CALL(s->engine->boot_distances(reps, seed, weights, pitch, weights_out, dist_out))
+}
+int pm_nj_trees(pm_session* s, int32_t n, int32_t count, const int32_t* dist, pm_nj_join* joins, pm_nj_last* last) {
+    if (!s) return fail(PM_EINVAL, "bad argument");
+    PM_STORE_CALL(s->engine->nj_trees(n, count, dist, (pm::NjJoinRec*)joins, (pm::NjLastRec*)last))
+}
+int pm_nj_support(pm_session* s, int32_t n, const pm_nj_join* main_joins, int32_t count, const pm_nj_join* rep_joins, int32_t* support) {
+    if (!s || (n > 3 && n <= pm::kNjMaxRows && (!main_joins || !support))) return fail(PM_EINVAL, "bad argument");
+    PM_STORE_CALL(s->engine->nj_support(n, (const pm::NjJoinRec*)main_joins, count, (const pm::NjJoinRec*)rep_joins, support))
+}
 int pm_session_traffic(const pm_session* s, uint64_t* h2d_bytes, uint64_t* d2h_bytes) {
     if (!s) return PM_EINVAL;
     if (h2d_bytes) *h2d_bytes = s->backend->bytes_h2d;

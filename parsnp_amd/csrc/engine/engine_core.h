@@ -30,6 +30,7 @@
 #include "index_kernels.h"
 #include "snp_kernels.h"
 #include "nj_kernels.h"
+#include "boot_kernels.h"
 
 namespace pm {
 
@@ -1795,7 +1796,7 @@ public:
     int snp_begin(int32_t n_rows) {
         if (n_rows < 2) { error = "a SNP collection needs at least 2 rows"; return -2; }
         if (n_rows > kSnpMaxRows) { error = "a SNP collection takes at most " + std::to_string(kSnpMaxRows) + " rows"; return -5; }
-        snp_rows = n_rows; snp_cols = 0; snp_v = 0; snp_up_bytes = 0; snp_dist_ready = false;
+        snp_rows = n_rows; snp_cols = 0; snp_v = 0; snp_up_bytes = 0; snp_dist_ready = false; boot_dist_ready = false;
         ensure(d_snp_counts, 4);
         ClearJob job{d_snp_counts.p, 4 * sizeof(uint64_t), 0};
         be.clear_many(&job, 1);
@@ -1805,7 +1806,7 @@ public:
         if (snp_rows < 2) { error = "no SNP collection has been started"; return -2; }
         if (snp_cols + n_cols >= ((int64_t)1 << 31)) { error = "a SNP collection takes fewer than 2^31 columns"; return -5; }
         timing.clear();
-        snp_dist_ready = false;
+        snp_dist_ready = false; boot_dist_ready = false;
         const size_t n = (size_t)snp_rows, nc = (size_t)n_cols;
         uint64_t counts[4] = {0, 0, 0, 0};
         if (n_cols) {
@@ -1929,6 +1930,171 @@ public:
         if (n > 3 && joins) be.d2h_async(joins, d_nj_joins.p, (N - 3) * sizeof(NjJoinRec));
         be.d2h_async(last, d_nj_last.p, sizeof(NjLastRec));
         be.sync();
+        collect_timing_more();
+        return 0;
+    }
+
+    // Bootstrap support of the SNP tree (boot_kernels.h).  Replicates are worked off in batches: the draw counters
+    // of a batch stay within kBootCounterBytes and the D matrices of a batch of trees within kBootTreeBytes ("boot_batch" forces the
+    // size; no result depends on it).  The replicate distances and the join records of all replicates stay on the device for the
+    // next call.  Nothing here touches the state of snp_distances / nj_tree.
+    static constexpr size_t kBootCounterBytes = (size_t)256 << 20, kBootTreeBytes = (size_t)1 << 30;
+    int64_t boot_batch = 0;      // pm_session_tune "boot_batch": replicates (trees) per batch, 0: the largest that fits
+    int boot_distances(int32_t reps, uint64_t seed, const uint8_t* weights, int64_t pitch, uint8_t* weights_out, int32_t* dist_out) {
+        if (snp_rows < 2) { error = "no SNP collection has been started"; return -2; }
+        if (reps < 1) { error = "a bootstrap needs at least 1 replicate"; return -2; }
+        if (reps > kBootMaxReps) { error = "a bootstrap takes at most " + std::to_string(kBootMaxReps) + " replicates"; return -5; }
+        const size_t n = (size_t)snp_rows, v = (size_t)snp_v, nrep = (size_t)reps;
+        if (weights) {
+            if (pitch < snp_v) { error = "the pitch of the weights is smaller than the number of core SNP columns"; return -2; }
+            for (size_t b = 0; b < nrep; b++)
+                for (size_t c = 0; c < v; c++)
+                    if (weights[b * (size_t)pitch + c] > kBootMaxWeight) { error = "a column weight above " + std::to_string(kBootMaxWeight); return -2; }
+        }
+        if (v * sizeof(uint32_t) > kBootCounterBytes) { error = "the draw counters of one replicate do not fit"; return -5; }
+        timing.clear();
+        boot_dist_ready = false;
+        ensure(d_boot_dist, nrep * n * n);
+        if (!v) {      // no column, no draw: every distance is 0
+            ClearJob job{d_boot_dist.p, 4 * nrep * n * n, 0};
+            be.clear_many(&job, 1);
+            if (dist_out) memset(dist_out, 0, 4 * nrep * n * n);
+            be.sync();
+            boot_dist_ready = true; boot_reps = reps;
+            return 0;
+        }
+        const size_t batch = std::min(nrep, boot_batch ? (size_t)boot_batch : kBootCounterBytes / (v * sizeof(uint32_t)));
+        const size_t words = (v + 63) / 64;
+        const int32_t tiles = (snp_rows + kSnpTile - 1) / kSnpTile;
+        ensure(d_boot_planes, batch * kBootPlanes * words); ensure(d_boot_w8, batch * v);
+        if (!weights) ensure(d_boot_cnt, batch * v);
+        std::vector<uint8_t> packed;
+        for (size_t b0 = 0; b0 < nrep; b0 += batch) {
+            const size_t nb = std::min(batch, nrep - b0);
+            be.mark("boot_draw");
+            if (weights) {
+                packed.resize(nb * v);
+                for (size_t b = 0; b < nb; b++) memcpy(packed.data() + b * v, weights + (b0 + b) * (size_t)pitch, v);
+                be.h2d(d_boot_w8.p, packed.data(), nb * v);
+            } else {
+                ClearJob job{d_boot_cnt.p, nb * v * sizeof(uint32_t), 0};
+                be.clear_many(&job, 1);
+                be.launch("boot_draw", (int64_t)(nb * v), BootDraw{seed, (int64_t)b0, snp_v, d_boot_cnt.p});
+            }
+            be.launch_wave("boot_pack", (int64_t)(nb * words), BootPack{d_boot_cnt.p, weights ? d_boot_w8.p : nullptr, snp_v, (int64_t)words, d_boot_w8.p, d_boot_planes.p});
+            be.mark("boot_dist");
+            const int64_t groups = ((int64_t)nb + kBootGroup - 1) / kBootGroup;
+            be.launch_wave("snp_dist_boot", (int64_t)tiles * tiles * groups,
+                           SnpDistBoot{d_snp_lo.p, d_snp_hi.p, snp_rows, (int64_t)words, tiles, d_boot_planes.p, (int32_t)nb, d_boot_dist.p + b0 * n * n});
+            be.mark(nullptr);
+            if (weights_out && !weights) be.d2h_async(weights_out + b0 * v, d_boot_w8.p, nb * v);      // (queued in front of the next batch's launches)
+        }
+        if (weights && weights_out) for (size_t b = 0; b < nrep; b++) memcpy(weights_out + b * v, weights + b * (size_t)pitch, v);
+        if (dist_out) be.d2h_async(dist_out, d_boot_dist.p, 4 * nrep * n * n);
+        be.sync();
+        collect_timing_more();
+        boot_dist_ready = true; boot_reps = reps;
+        return 0;
+    }
+    int32_t boot_reps = 0; bool boot_dist_ready = false;      // replicate distances of boot_reps x snp_rows x snp_rows are on the device
+    int32_t boot_trees = 0, boot_trees_n = 0;                 // join records of boot_trees trees of boot_trees_n leaves are on the device
+
+    static const char* nj_matrix_fault(const int32_t* dist, size_t N) {
+        for (size_t i = 0; i < N; i++) {
+            if (dist[i * N + i] != 0) return "the distance matrix has a non-zero diagonal";
+            for (size_t j = i + 1; j < N; j++) {
+                if (dist[i * N + j] < 0) return "the distance matrix has a negative entry";
+                if (dist[i * N + j] != dist[j * N + i]) return "the distance matrix is not symmetric";
+            }
+        }
+        return nullptr;
+    }
+    // count trees of one n, the trees of a batch in lock step: 2 (n - 3) + 2 launches a batch, no wait before the download
+    int nj_trees(int32_t n, int32_t count, const int32_t* dist, NjJoinRec* joins, NjLastRec* last) {
+        if (n < 3) { error = "a neighbour-joining tree needs at least 3 rows"; return -2; }
+        if (n > kNjMaxRows) { error = "a neighbour-joining tree takes at most " + std::to_string(kNjMaxRows) + " rows"; return -5; }
+        if (count < 1) { error = "at least 1 tree"; return -2; }
+        if (count > kBootMaxReps) { error = "at most " + std::to_string(kBootMaxReps) + " trees a call"; return -5; }
+        const size_t N = (size_t)n, cnt = (size_t)count, M = N - 3;
+        if (!dist) {
+            if (!boot_dist_ready || snp_rows != n || count > boot_reps) { error = "no distances of " + std::to_string(count) + " replicates of " + std::to_string(n) + " rows have been computed in this session"; return -2; }
+        } else {
+            for (size_t b = 0; b < cnt; b++)
+                if (const char* fault = nj_matrix_fault(dist + b * N * N, N)) { error = fault; return -2; }
+        }
+        if (N * N * sizeof(double) > kBootTreeBytes) { error = "the matrix of one tree does not fit"; return -5; }
+        timing.clear();
+        boot_trees = 0;
+        const size_t batch = std::min(cnt, boot_batch ? (size_t)boot_batch : kBootTreeBytes / (N * N * sizeof(double)));
+        ensure(d_bt_D, batch * N * N); ensure(d_bt_R, batch * N); ensure(d_bt_active, batch * N); ensure(d_bt_q, batch * N); ensure(d_bt_j, batch * N);
+        ensure(d_bt_joins, cnt * M + 1); ensure(d_bt_last, cnt);
+        if (dist) ensure(d_bt_dist, batch * N * N);
+        for (size_t b0 = 0; b0 < cnt; b0 += batch) {
+            const size_t nb = std::min(batch, cnt - b0);
+            const int32_t* src = d_boot_dist.p + b0 * N * N;
+            if (dist) { be.h2d(d_bt_dist.p, dist + b0 * N * N, 4 * nb * N * N); src = d_bt_dist.p; }
+            be.mark("boot_nj");
+            be.launch_wave("nj_init_b", (int64_t)(nb * N), NjInitB{src, n, d_bt_D.p, d_bt_R.p, d_bt_active.p});
+            for (int32_t t = 0; t + 3 < n; t++) {
+                const int32_t r = n - t;
+                be.launch_wave("nj_rowmin_b", (int64_t)(nb * N), NjRowMinB{d_bt_D.p, d_bt_R.p, d_bt_active.p, n, r, d_bt_q.p, d_bt_j.p});
+                be.launch("nj_join_b", (int64_t)nb * kNjGroup, NjJoinB{d_bt_D.p, d_bt_R.p, d_bt_active.p, n, r, d_bt_q.p, d_bt_j.p, d_bt_joins.p + b0 * M, t});
+            }
+            be.launch_wave("nj_last_b", (int64_t)nb, NjLastB{d_bt_D.p, d_bt_active.p, n, d_bt_last.p + b0});
+            be.mark(nullptr);
+        }
+        if (M && joins) be.d2h_async(joins, d_bt_joins.p, cnt * M * sizeof(NjJoinRec));
+        if (last) be.d2h_async(last, d_bt_last.p, cnt * sizeof(NjLastRec));
+        be.sync();
+        collect_timing_more();
+        boot_trees = count; boot_trees_n = n;
+        return 0;
+    }
+    // a caller's n - 3 records: 0 <= i < j < n, both slots still active
+    static bool nj_records_valid(const NjJoinRec* J, size_t N, std::vector<uint8_t>& active) {
+        active.assign(N, 1);
+        for (size_t t = 0; t + 3 < N; t++) {
+            const int32_t i = J[t].i, j = J[t].j;
+            if (i < 0 || j <= i || (size_t)j >= N || !active[(size_t)i] || !active[(size_t)j]) return false;
+            active[(size_t)j] = 0;
+        }
+        return true;
+    }
+    // support[t]: in how many of the count trees the split of join t of the main tree occurs (as a set of leaves)
+    int nj_support(int32_t n, const NjJoinRec* main_joins, int32_t count, const NjJoinRec* rep_joins, int32_t* support) {
+        if (n < 3) { error = "a neighbour-joining tree needs at least 3 rows"; return -2; }
+        if (n > kNjMaxRows) { error = "a neighbour-joining tree takes at most " + std::to_string(kNjMaxRows) + " rows"; return -5; }
+        if (count < 1) { error = "at least 1 tree"; return -2; }
+        if (count > kBootMaxReps) { error = "at most " + std::to_string(kBootMaxReps) + " trees a call"; return -5; }
+        if (n == 3) return 0;      // no internal branch
+        const size_t N = (size_t)n, cnt = (size_t)count, M = N - 3, W = (N + 63) / 64;
+        std::vector<uint8_t> scratch;
+        if (!nj_records_valid(main_joins, N, scratch)) { error = "a join record of the main tree is not a join of two active slots"; return -2; }
+        if (rep_joins) {
+            for (size_t b = 0; b < cnt; b++)
+                if (!nj_records_valid(rep_joins + b * M, N, scratch)) { error = "a join record of tree " + std::to_string(b) + " is not a join of two active slots"; return -2; }
+        } else if (boot_trees_n != n || count > boot_trees) { error = "no records of " + std::to_string(count) + " trees of " + std::to_string(n) + " leaves are on the device"; return -2; }
+        timing.clear();
+        const size_t batch = std::min(cnt, boot_batch ? (size_t)boot_batch : std::max<size_t>(1, kBootTreeBytes / (N * N * sizeof(double))));
+        ensure(d_bs_mj, M); ensure(d_bs_msets, M * W); ensure(d_bs_mkeys, M); ensure(d_bs_support, M);
+        ensure(d_bs_rsets, batch * M * W); ensure(d_bs_rkeys, batch * M);
+        if (rep_joins) ensure(d_bs_rj, batch * M);
+        be.h2d(d_bs_mj.p, main_joins, M * sizeof(NjJoinRec));
+        be.mark("boot_support");
+        ClearJob job{d_bs_support.p, M * sizeof(uint32_t), 0};
+        be.clear_many(&job, 1);
+        be.launch_wave("boot_splits", 1, BootSplits{d_bs_mj.p, n, (int32_t)W, d_bs_msets.p, d_bs_mkeys.p});
+        be.mark(nullptr);
+        for (size_t b0 = 0; b0 < cnt; b0 += batch) {
+            const size_t nb = std::min(batch, cnt - b0);
+            const NjJoinRec* src = d_bt_joins.p + b0 * M;
+            if (rep_joins) { be.h2d(d_bs_rj.p, rep_joins + b0 * M, nb * M * sizeof(NjJoinRec)); src = d_bs_rj.p; }
+            be.mark("boot_support");
+            be.launch_wave("boot_splits", (int64_t)nb, BootSplits{src, n, (int32_t)W, d_bs_rsets.p, d_bs_rkeys.p});
+            be.launch_wave("boot_match", (int64_t)nb, BootMatch{d_bs_msets.p, d_bs_mkeys.p, d_bs_rsets.p, d_bs_rkeys.p, n, (int32_t)W, d_bs_support.p});
+            be.mark(nullptr);
+        }
+        be.d2h(support, d_bs_support.p, M * sizeof(int32_t));
         collect_timing_more();
         return 0;
     }
@@ -2059,6 +2225,7 @@ public:
         if (key == "dirty_min" && value >= 0) { dirty_min = value; return true; }
         if (key == "hint_shrink" && value >= 1) { hint_shrink = value; return true; }
         if (key == "copy_kernel") { return tune_copy_kernel(be, value != 0, 0); }
+        if (key == "boot_batch" && value >= 0) { boot_batch = value; return true; }
         return false;
     }
 
@@ -2149,6 +2316,9 @@ private:
     Buf<uint64_t> d_image;
     Buf<int64_t> d_un_blk, d_un_cnt, d_un_scan, d_un_tot; Buf<int32_t> d_un_out;      // the unaligned runs: block geometry, counts per block, their scans, totals per genome, the runs
     Buf<double> d_nj_D, d_nj_R, d_nj_q; Buf<uint8_t> d_nj_active; Buf<int32_t> d_nj_j, d_nj_dist; Buf<NjJoinRec> d_nj_joins; Buf<NjLastRec> d_nj_last;      // a neighbour-joining tree (nj_kernels.h)
+    // the bootstrap (boot_kernels.h): draw counters, weights as bytes and planes, replicate distances; the trees of a batch; splits and support
+    Buf<uint32_t> d_boot_cnt, d_bs_support; Buf<uint8_t> d_boot_w8, d_bt_active; Buf<uint64_t> d_boot_planes, d_bs_msets, d_bs_mkeys, d_bs_rsets, d_bs_rkeys;
+    Buf<int32_t> d_boot_dist, d_bt_dist, d_bt_j; Buf<double> d_bt_D, d_bt_R, d_bt_q; Buf<NjJoinRec> d_bt_joins, d_bs_mj, d_bs_rj; Buf<NjLastRec> d_bt_last;
     Buf<uint64_t> d_snp_counts, d_snp_lo, d_snp_hi; Buf<uint8_t> d_snp_chunk; Buf<int64_t> d_snp_flag, d_snp_rank, d_snp_col; Buf<int32_t> d_snp_dist;      // the SNP collection (snp_kernels.h)
     Buf<uint8_t> d_ms_strand, d_ms_state, d_small8, d_o_strand; Buf<int32_t> d_ms_shift, d_ms_len, d_list, d_list2, d_j_min, d_j_max, d_o_start;
     Buf<int64_t> d_rg_start, d_rg_len, d_lay_off, d_lay_bits, d_v_row0, d_v_first, d_f_start, d_f_end, d_f_pack; Buf<RegInfo> d_rg_info; Buf<uint64_t> d_rg_count, d_once, d_twice;

@@ -49,6 +49,8 @@ struct Params {
     int c = 0, d = 0, q = 0, p = 0, do_align = 0, cores = 2, random = 0;
     bool unaligned = false, recomb_filter = false, anchors_only = false, calc_mumi = false, extend_mums = false;
     bool snps = false;      // [Output] snps: core SNP columns and SNP distances beside the XMFA (snps.cpp); the reference ignores the key
+    int bootstrap = 0;      // [Output] bootstrap=B: B bootstrap replicates label the tree's branches with their support (tree.cpp); implies tree
+    uint64_t bootseed = 1;  // [Output] bootseed: the seed of the replicates' draws
     bool tree = false;      // [Output] tree: the neighbour-joining tree of the SNP distances beside them (tree.cpp); implies snps
     float diag_diff = 1.0f, factor = 0.0f;
     std::string anchors, mums, anchorfile, mumfile, prefix, outdir;
@@ -531,7 +533,8 @@ public:
     long commit(int cluster, long c0, size_t width, const int64_t* ref_pos, int64_t ref_base);
     // the three files beside the XMFA, the console line, snp_counts
     // (tree: then the neighbour-joining tree of the distances, which are still on the device -- tree.cpp)
-    void finish(const std::vector<Genome>& genomes, const std::string& dir, const std::string& stem, bool tree = false);
+    // (bootstrap > 0: then the tree once more with the support of bootstrap replicates on its branches)
+    void finish(const std::vector<Genome>& genomes, const std::string& dir, const std::string& stem, bool tree = false, int bootstrap = 0, uint64_t bootseed = 1);
 
 private:
     struct Entry { int64_t first; int32_t cluster; int32_t width; int64_t c0; };      // columns [first, first + width) of all columns handed over
@@ -546,13 +549,17 @@ private:
 
 // The neighbour-joining tree of the SNP distances ([Output] tree=1; tree.cpp): the engine joins (pm_nj_tree over the
 // distances the session has just computed), the host turns the join records into branch lengths and one line of Newick.
-struct TreeCounts { bool on = false; double nj_ms = 0; long joins = 0; };
+struct TreeCounts { bool on = false; double nj_ms = 0; long joins = 0; bool boot_on = false; long boot_reps = 0; double boot_ms = 0; };
 extern TreeCounts tree_counts;      // what the last write_output built (PARSNP_TIMING: nj_*, with tree=1 only)
 int tree_max_rows();                // sequences a run with tree=1 may have
+int boot_max_reps();                // replicates a run with bootstrap=B may ask for
 // the Newick line (without the newline) of n >= 3 names from the engine's records
-std::string nj_newick(const std::vector<std::string>& names, const pm_nj_join* joins, const pm_nj_last& last);
+// (support: null, or a label per join)
+std::string nj_newick(const std::vector<std::string>& names, const pm_nj_join* joins, const pm_nj_last& last, const int32_t* support = nullptr);
 // <stem>.snps.nwk; dist: the n x n distances on the host (read for n == 2 only: the engine is not called then)
-void write_tree(pm_session* session, const std::vector<std::string>& names, const int32_t* dist, const std::string& dir, const std::string& stem);
+// bootstrap > 0: then <stem>.snps.boot.nwk, the same text with the support of join t behind its node
+void write_tree(pm_session* session, const std::vector<std::string>& names, const int32_t* dist, const std::string& dir, const std::string& stem,
+                int bootstrap = 0, uint64_t bootseed = 1);
 
 std::string reverse_complement(const std::string& s);   // Aligner::reversec, :1294-1393
 

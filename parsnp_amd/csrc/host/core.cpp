@@ -47,6 +47,9 @@ int CoreRun::open(const std::string& ini_path) {
     prm.outdir = ini.get("Output", "outdir", "output");
     prm.snps = ini.get_bool("Output", "snps");
     prm.tree = ini.get_bool("Output", "tree");
+    prm.bootstrap = ini.get_int("Output", "bootstrap");      // absent or 0: off
+    prm.bootseed = strtoull(ini.get("Output", "bootseed", "1").c_str(), nullptr, 10);
+    if (prm.bootstrap > 0) prm.tree = true;      // (the support values label the branches of the tree)
     if (prm.tree) prm.snps = true;      // (the tree is built over the SNP distances)
     const bool reverse_ref = ini.get_bool("Reference", "reverse");
     qfiles = (int)ini.count("Query") / 2;
@@ -63,6 +66,10 @@ int CoreRun::open(const std::string& ini_path) {
     }
     if (prm.tree && qfiles + 1 > tree_max_rows()) {
         std::cerr << "parsnp_core: input exceeds a limit of the multi-MUM engine: tree=1 takes at most " << tree_max_rows() << " sequences" << std::endl;
+        return 5;
+    }
+    if (prm.bootstrap > boot_max_reps()) {
+        std::cerr << "parsnp_core: input exceeds a limit of the multi-MUM engine: bootstrap takes at most " << boot_max_reps() << " replicates" << std::endl;
         return 5;
     }
 

@@ -167,6 +167,8 @@ int main(int argc, char* argv[]) {
                         snp_counts.columns, snp_counts.core, snp_counts.other, snp_counts.h2d_bytes, snp_counts.scan_ms, snp_counts.dist_ms);
             if (tree_counts.on)      // (tree=1 only)
                 fprintf(f, ", \"nj_ms\": %.3f, \"nj_joins\": %ld", tree_counts.nj_ms, tree_counts.joins);
+            if (tree_counts.boot_on)      // (bootstrap=B only)
+                fprintf(f, ", \"boot_reps\": %ld, \"boot_ms\": %.3f", tree_counts.boot_reps, tree_counts.boot_ms);
             fprintf(f, "}\n");
             fclose(f);
         }

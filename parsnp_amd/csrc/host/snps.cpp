@@ -96,7 +96,7 @@ void SnpCollector::flush() {
     used_ = 0;
 }
 
-void SnpCollector::finish(const std::vector<Genome>& genomes, const std::string& dir, const std::string& stem, bool tree) {
+void SnpCollector::finish(const std::vector<Genome>& genomes, const std::string& dir, const std::string& stem, bool tree, int bootstrap, uint64_t bootseed) {
     flush();
     const size_t v = (size_t)counts_.core_snps;
     std::vector<int64_t> col(v);
@@ -146,7 +146,7 @@ void SnpCollector::finish(const std::vector<Genome>& genomes, const std::string&
     if (tree) {      // (the last engine call was pm_snp_distances: its matrix is what the tree is built over)
         std::vector<std::string> names;
         for (size_t i = 0; i < n_; i++) names.push_back(genomes[i].fname);
-        write_tree(session_, names, dist.data(), dir, stem);
+        write_tree(session_, names, dist.data(), dir, stem, bootstrap, bootseed);
     }
     snp_counts.on = true;
     snp_counts.columns = (long)counts_.columns + invariant_; snp_counts.invariant = (long)counts_.core_invariant + invariant_;

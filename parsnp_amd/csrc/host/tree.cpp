@@ -10,6 +10,11 @@
 // with AVX2 and WITHOUT FMA (no -mfma, no -march=native: csrc/Makefile), so the compiler has no fused instruction to contract these
 // into; each result additionally passes through `once`, an empty asm statement the optimiser cannot see through.
 // Lengths are not clamped (a negative one is printed as it is); the unit is core SNP columns.
+//
+// [Output] bootstrap=B: after the main tree the engine draws B replicates of the core SNP columns, computes their
+// weighted distances (pm_boot_distances), joins the B replicate trees in lock step (pm_nj_trees) and counts, for every join of the
+// main tree, the replicate trees that hold its split (pm_nj_support).  Nothing but the n - 3 counts comes back.  <stem>.snps.boot.nwk
+// is the same Newick text with the count of join t behind the closing bracket of its node; <stem>.snps.nwk keeps its bytes.
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -20,6 +25,10 @@
 // Weak, like the pm_snp_* calls: a provider of the ABI without them still links; tree=1 then ends the run.
 extern "C" int pm_nj_limits(int* max_rows) __attribute__((weak));
 extern "C" int pm_nj_tree(pm_session* s, int32_t n, const int32_t* dist, pm_nj_join* joins, pm_nj_last* last) __attribute__((weak));
+extern "C" int pm_boot_limits(int* max_rows, int* max_reps, int* max_weight) __attribute__((weak));
+extern "C" int pm_boot_distances(pm_session* s, int32_t reps, uint64_t seed, const uint8_t* weights, int64_t pitch, uint8_t* weights_out, int32_t* dist_out) __attribute__((weak));
+extern "C" int pm_nj_trees(pm_session* s, int32_t n, int32_t count, const int32_t* dist, pm_nj_join* joins, pm_nj_last* last) __attribute__((weak));
+extern "C" int pm_nj_support(pm_session* s, int32_t n, const pm_nj_join* main_joins, int32_t count, const pm_nj_join* rep_joins, int32_t* support) __attribute__((weak));
 
 namespace parsnp {
 TreeCounts tree_counts;
@@ -58,9 +67,15 @@ int tree_max_rows() {
     return rows;
 }
 
+int boot_max_reps() {
+    int reps = 1024;
+    if (pm_boot_limits) (void)pm_boot_limits(nullptr, &reps, nullptr);
+    return reps;
+}
+
 // Every slot holds the text of its subtree; a join replaces slot i's by the new node's.  No recursion: a caterpillar of 2 046 joins
 // is 2 046 passes of this loop.
-std::string nj_newick(const std::vector<std::string>& names, const pm_nj_join* joins, const pm_nj_last& last) {
+std::string nj_newick(const std::vector<std::string>& names, const pm_nj_join* joins, const pm_nj_last& last, const int32_t* support) {
     const size_t n = names.size();
     std::vector<std::string> slot(n);
     for (size_t i = 0; i < n; i++) slot[i] = newick_name(names[i]);
@@ -72,6 +87,7 @@ std::string nj_newick(const std::vector<std::string>& names, const pm_nj_join* j
         std::string node = "(";
         node += slot[(size_t)J.i]; node += ':'; put_length(node, li); node += ',';
         node += slot[(size_t)J.j]; node += ':'; put_length(node, lj); node += ')';
+        if (support) node += std::to_string(support[t]);
         slot[(size_t)J.i].swap(node);
         std::string().swap(slot[(size_t)J.j]);
     }
@@ -85,9 +101,12 @@ std::string nj_newick(const std::vector<std::string>& names, const pm_nj_join* j
     return out;
 }
 
-void write_tree(pm_session* session, const std::vector<std::string>& names, const int32_t* dist, const std::string& dir, const std::string& stem) {
+void write_tree(pm_session* session, const std::vector<std::string>& names, const int32_t* dist, const std::string& dir, const std::string& stem,
+                int bootstrap, uint64_t bootseed) {
     const size_t n = names.size();
-    std::string text;
+    std::string text, boot_text;
+    long boot_reps = 0;
+    double boot_ms = 0;
     long joins_made = 0;
     double ms = 0;
     if (n == 2) {      // no device call: the one distance, halved
@@ -115,12 +134,39 @@ void write_tree(pm_session* session, const std::vector<std::string>& names, cons
             for (int i = 0; i < cnt; i++) if (!strcmp(tn[i], "nj")) ms += tms[i];
         joins_made = (long)n - 3;
         text = nj_newick(names, joins.data(), last);
+        if (bootstrap > 0 && n > 3) {      // (three leaves have no internal branch: no label, no call)
+            if (!pm_boot_distances || !pm_nj_trees || !pm_nj_support) {
+                std::cerr << "parsnp_core: this provider of the engine's ABI cannot bootstrap a tree (bootstrap=" << bootstrap << ")" << std::endl;
+                exit(1);
+            }
+            std::vector<int32_t> support(n - 3);
+            auto step = [&](int rc, const char* what) {
+                if (rc != PM_OK) {
+                    std::cerr << "parsnp_core: cannot bootstrap the tree (" << what << "): " << pm_last_error() << std::endl;
+                    exit(rc == PM_ELIMIT ? 5 : 1);
+                }
+                int c = 64; const char* tn2[64]; float tms2[64];
+                if (pm_last_timing(session, &c, tn2, tms2) == PM_OK)
+                    for (int i = 0; i < c; i++) if (!strncmp(tn2[i], "boot_", 5)) boot_ms += tms2[i];
+            };
+            step(pm_boot_distances(session, bootstrap, bootseed, nullptr, 0, nullptr, nullptr), "distances");
+            step(pm_nj_trees(session, (int32_t)n, bootstrap, nullptr, nullptr, nullptr), "trees");
+            step(pm_nj_support(session, (int32_t)n, joins.data(), bootstrap, nullptr, support.data()), "support");
+            boot_reps = bootstrap;
+            boot_text = nj_newick(names, joins.data(), last, support.data());
+        }
     }
     text += '\n';
     std::ofstream out((dir + stem + ".snps.nwk").c_str(), std::ios::binary);
     out << text;
     tree_counts.on = true; tree_counts.nj_ms = ms; tree_counts.joins = joins_made;
     std::cerr << "Neighbour-joining tree: " << n << " leaves, " << joins_made << " joins on the device" << std::endl;
+    if (bootstrap > 0) {
+        std::ofstream bout((dir + stem + ".snps.boot.nwk").c_str(), std::ios::binary);
+        bout << (boot_reps ? boot_text + '\n' : text);
+        tree_counts.boot_on = true; tree_counts.boot_reps = boot_reps; tree_counts.boot_ms = boot_ms;
+        if (boot_reps) std::cerr << "Bootstrap: " << boot_reps << " replicates of " << n << " leaves on the device" << std::endl;
+    }
 }
 
 }  // namespace parsnp

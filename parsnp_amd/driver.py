@@ -51,10 +51,12 @@ def driver_order(paths):
     return out
 
 
-def ini_text(ref, queries, outdir, snps=None, tree=None, **kw):
+def ini_text(ref, queries, outdir, snps=None, tree=None, bootstrap=None, bootseed=None, **kw):
     """snps=1: `snps=1` under [Output] (core SNP columns and SNP distances beside the XMFA: read_snps; the reference ignores the
-    key).  tree=1: `tree=1` there (it implies snps=1: the neighbour-joining tree of the SNP distances, read_tree).  Without the
-    arguments the text is the reference driver's, byte for byte."""
+    key).  tree=1: `tree=1` there (it implies snps=1: the neighbour-joining tree of the SNP distances, read_tree).  bootstrap=B:
+    `bootstrap=B` there (it implies tree=1: the tree once more with the support of B bootstrap replicates on its branches,
+    read_boot_tree); bootseed=S: the seed of the replicates (default 1).  Without the arguments the text is the reference
+    driver's, byte for byte."""
     p = dict(DEFAULTS, **kw)
     files = "".join("file%d=%s\nreverse%d=0\n" % (i, q, i) for i, q in enumerate(queries, 1))
     text = _TEMPLATE.format(ref=ref, files=files, outdir=outdir, **p)
@@ -62,6 +64,10 @@ def ini_text(ref, queries, outdir, snps=None, tree=None, **kw):
         text += "snps=%d\n" % int(snps)
     if tree is not None:
         text += "tree=%d\n" % int(tree)
+    if bootstrap is not None:
+        text += "bootstrap=%d\n" % int(bootstrap)
+    if bootseed is not None:
+        text += "bootseed=%d\n" % int(bootseed)
     return text
 
 
@@ -114,5 +120,13 @@ def read_snps(outdir, stem="parsnpAligner"):
 def read_tree(outdir, stem="parsnpAligner"):
     """the Newick string a run with tree=1 leaves beside the SNP files (one line: the file without its newline)"""
     text = open(os.path.join(outdir, stem + ".snps.nwk")).read()
+    assert text.endswith(";\n") and text.count("\n") == 1
+    return text[:-1]
+
+
+def read_boot_tree(outdir, stem="parsnpAligner"):
+    """the Newick string a run with bootstrap=B leaves beside the tree: the text of read_tree with the number of replicate trees that
+    hold a branch behind the closing bracket of its node (one line: the file without its newline)"""
+    text = open(os.path.join(outdir, stem + ".snps.boot.nwk")).read()
     assert text.endswith(";\n") and text.count("\n") == 1
     return text[:-1]
