@@ -393,6 +393,28 @@ int pm_boot_limits(int* max_rows, int* max_reps, int* max_weight);
 int pm_boot_distances(pm_session* s, int32_t reps, uint64_t seed, const uint8_t* weights, int64_t pitch, uint8_t* weights_out, int32_t* dist_out);
 int pm_nj_trees(pm_session* s, int32_t n, int32_t count, const int32_t* dist, pm_nj_join* joins, pm_nj_last* last);
 int pm_nj_support(pm_session* s, int32_t n, const pm_nj_join* main_joins, int32_t count, const pm_nj_join* rep_joins, int32_t* support);
+/* Recombination scan of the session's SNP collection (DEFINED in INTEGRATION.md 1d; all integers, exact): the pairwise homoplasy
+ * index of windows of sites and its permutation test.  The limits call reports the rows (2 048), the sites of a window (256) and the
+ * permutations of a call (65 536); it needs no device.
+ * pm_rec_sites: informative[v] (uint8 [V], may be NULL) = 1 where core SNP column v has at least two letters that each occur in at
+ * least two rows; n_informative: their number.  The collection's distances need not have been computed.  The planes transposed
+ * for this (per column a bit set over the rows) stay on the device until the collection changes.  Phase `rec_sites`.
+ * pm_rec_incompat: for every window w (sites[win_off[w]] ... sites[win_off[w + 1] - 1], indices into the V core SNP columns in any
+ * order, informative or not) the k x k byte matrix of the pair scores `inc` of 1d, the diagonal 0.  inc_out: the matrices packed one
+ * after the other (sum of k^2 bytes), may be NULL; they stay on the device for pm_rec_test.  Phase `rec_incompat`.
+ * pm_rec_test: phi[w] = T(identity) and le[w] = the number of the `perms` permutations with T <= phi, for windows of the sizes
+ * win_off gives.  inc: the caller's packed matrices, or NULL for those of the last pm_rec_incompat (the sizes must be its).
+ * win_id[w]: the window's number g (its keys come from seed + g), NULL: 0, 1, ...  Phase `rec_permute`.
+ * PM_EINVAL: no collection started (sites, incompat), a site outside 0 ... V - 1, a win_off that does not ascend or leaves the site
+ * list, a window of fewer than 2 sites, near < 1, perms < 1, inc NULL without matrices of these sizes on the device.  PM_ELIMIT: a
+ * window of more than 256 sites, perms > 65 536, more than 1 GiB of matrices in one call.  n_windows == 0 is valid and launches
+ * nothing.  Windows are worked off in batches; pm_session_tune(s, "rec_batch", k) forces k a batch (0: the default); no result
+ * depends on k.  Everything of one call is queued without a wait in between. */
+int pm_rec_limits(int* max_rows, int* max_window_sites, int* max_perms);
+int pm_rec_sites(pm_session* s, uint8_t* informative, int64_t* n_informative);
+int pm_rec_incompat(pm_session* s, int64_t n_sites, const int64_t* sites, int64_t n_windows, const int64_t* win_off, uint8_t* inc_out);
+int pm_rec_test(pm_session* s, int64_t n_windows, const int64_t* win_off, const uint8_t* inc, int32_t near, int32_t perms, uint64_t seed,
+                const int64_t* win_id, int32_t* phi, int32_t* le);
 /* bytes this session has moved over the host link so far (every copy the engine issued, both directions) */
 int pm_session_traffic(const pm_session* s, uint64_t* h2d_bytes, uint64_t* d2h_bytes);
 

@@ -94,6 +94,11 @@ class Lib:
         pm_boot_limits"""
         return self._gap_limits_of("pm_boot_limits")
 
+    def rec_limits(self):
+        """(rows, sites of a window, permutations of a call) of the recombination scan (Session.rec_sites, rec_incompat, rec_test):
+        pm_rec_limits"""
+        return self._gap_limits_of("pm_rec_limits")
+
     def _gap_limits_of(self, name):
         if not hasattr(self.L, name):
             raise PmError("this provider of the ABI has no %s" % name)
@@ -298,6 +303,63 @@ class Session:
         self.lib._check(L.pm_nj_support(self.h, n, main_joins.ctypes.data_as(v), count, rep_joins.ctypes.data_as(v) if rep_joins is not None else None,
                                         support.ctypes.data_as(v)))
         return support
+
+    def _rec_fn(self, name, argtypes):
+        L = self.lib.L
+        if not hasattr(L, name):
+            raise PmError("this provider of the ABI has no %s" % name)
+        fn = getattr(L, name)
+        fn.argtypes = argtypes
+        return fn
+
+    def rec_sites(self):
+        """pm_rec_sites -> uint8 [V]: 1 where a core SNP column of the last core_snps of this session is informative (INTEGRATION.md
+        1d).  The transposed planes stay on the device for rec_incompat()."""
+        v = C.c_void_p
+        fn = self._rec_fn("pm_rec_sites", [v, v, v])
+        flags, count = np.zeros(int(getattr(self, "_snp_core", 0)), np.uint8), C.c_int64(-1)
+        self.lib._check(fn(self.h, flags.ctypes.data_as(v), C.byref(count)))
+        assert count.value == int(flags.sum())
+        return flags
+
+    @staticmethod
+    def _rec_offsets(win_off):
+        win_off = np.ascontiguousarray(win_off, np.int64)
+        assert win_off.ndim == 1 and len(win_off) >= 1
+        return win_off, len(win_off) - 1
+
+    def rec_incompat(self, sites, win_off):
+        """pm_rec_incompat -> list of uint8 [k, k]: the pair scores of every window sites[win_off[w]:win_off[w + 1]] (indices into
+        the core SNP columns).  The matrices stay on the device for rec_test()."""
+        v = C.c_void_p
+        fn = self._rec_fn("pm_rec_incompat", [v, C.c_int64, v, C.c_int64, v, v])
+        sites = np.ascontiguousarray(sites, np.int64)
+        win_off, nw = self._rec_offsets(win_off)
+        k = np.diff(win_off)
+        ok = nw > 0 and bool((k >= 0).all()) and bool((k <= 4096).all())
+        out = np.zeros(int((k * k).sum()) if ok else 0, np.uint8)
+        self.lib._check(fn(self.h, len(sites), sites.ctypes.data_as(v), nw, win_off.ctypes.data_as(v), out.ctypes.data_as(v)))
+        at = np.concatenate(([0], np.cumsum(k * k))) if ok else [0]
+        return [out[at[w]:at[w + 1]].reshape(int(k[w]), int(k[w])) for w in range(nw)]
+
+    def rec_test(self, win_off, near=10, perms=1000, seed=1, inc=None, win_id=None):
+        """pm_rec_test -> (phi, le), int32 [windows] each: the statistic at identity order and the number of the `perms`
+        permutations that do not exceed it.  inc: a list of uint8 [k, k] (or their packed bytes), None: the matrices of the last
+        rec_incompat() on the device.  win_id: the windows' numbers g (int64), None: 0, 1, ..."""
+        v = C.c_void_p
+        fn = self._rec_fn("pm_rec_test", [v, C.c_int64, v, v, C.c_int32, C.c_int32, C.c_uint64, v, v, v])
+        win_off, nw = self._rec_offsets(win_off)
+        if inc is not None:
+            if isinstance(inc, (list, tuple)):
+                inc = np.concatenate([np.zeros(0, np.uint8)] + [np.asarray(m, np.uint8).ravel() for m in inc])
+            inc = np.ascontiguousarray(inc, np.uint8)
+        if win_id is not None:
+            win_id = np.ascontiguousarray(win_id, np.int64)
+            assert win_id.shape == (nw,)
+        phi, le = np.zeros(nw, np.int32), np.zeros(nw, np.int32)
+        self.lib._check(fn(self.h, nw, win_off.ctypes.data_as(v), inc.ctypes.data_as(v) if inc is not None else None, near, perms, seed & (2 ** 64 - 1),
+                           win_id.ctypes.data_as(v) if win_id is not None else None, phi.ctypes.data_as(v), le.ctypes.data_as(v)))
+        return phi, le
 
     def __enter__(self):
         return self

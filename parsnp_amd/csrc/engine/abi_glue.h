@@ -331,6 +331,26 @@ int pm_nj_support(pm_session* s, int32_t n, const pm_nj_join* main_joins, int32_
     if (!s || (n > 3 && n <= pm::kNjMaxRows && (!main_joins || !support))) return fail(PM_EINVAL, "bad argument");
     PM_STORE_CALL(s->engine->nj_support(n, (const pm::NjJoinRec*)main_joins, count, (const pm::NjJoinRec*)rep_joins, support))
 }
+// recombination scan of the SNP collection (rec_kernels.h)
+int pm_rec_limits(int* max_rows, int* max_window_sites, int* max_perms) {
+    if (max_rows) *max_rows = pm::kSnpMaxRows;
+    if (max_window_sites) *max_window_sites = pm::kRecMaxSites;
+    if (max_perms) *max_perms = pm::kRecMaxPerms;
+    return PM_OK;
+}
+int pm_rec_sites(pm_session* s, uint8_t* informative, int64_t* n_informative) {
+    if (!s) return fail(PM_EINVAL, "bad argument");
+    PM_STORE_CALL(s->engine->rec_sites(informative, n_informative))
+}
+int pm_rec_incompat(pm_session* s, int64_t n_sites, const int64_t* sites, int64_t n_windows, const int64_t* win_off, uint8_t* inc_out) {
+    if (!s) return fail(PM_EINVAL, "bad argument");
+    PM_STORE_CALL(s->engine->rec_incompat(n_sites, sites, n_windows, win_off, inc_out))
+}
+int pm_rec_test(pm_session* s, int64_t n_windows, const int64_t* win_off, const uint8_t* inc, int32_t near, int32_t perms, uint64_t seed,
+                const int64_t* win_id, int32_t* phi, int32_t* le) {
+    if (!s) return fail(PM_EINVAL, "bad argument");
+    PM_STORE_CALL(s->engine->rec_test(n_windows, win_off, inc, near, perms, seed, win_id, phi, le))
+}
 int pm_session_traffic(const pm_session* s, uint64_t* h2d_bytes, uint64_t* d2h_bytes) {
     if (!s) return PM_EINVAL;
     if (h2d_bytes) *h2d_bytes = s->backend->bytes_h2d;

@@ -31,6 +31,7 @@
 #include "snp_kernels.h"
 #include "nj_kernels.h"
 #include "boot_kernels.h"
+#include "rec_kernels.h"
 
 namespace pm {
 
@@ -1796,7 +1797,7 @@ public:
     int snp_begin(int32_t n_rows) {
         if (n_rows < 2) { error = "a SNP collection needs at least 2 rows"; return -2; }
         if (n_rows > kSnpMaxRows) { error = "a SNP collection takes at most " + std::to_string(kSnpMaxRows) + " rows"; return -5; }
-        snp_rows = n_rows; snp_cols = 0; snp_v = 0; snp_up_bytes = 0; snp_dist_ready = false; boot_dist_ready = false;
+        snp_rows = n_rows; snp_cols = 0; snp_v = 0; snp_up_bytes = 0; snp_dist_ready = false; boot_dist_ready = false; rec_forget();
         ensure(d_snp_counts, 4);
         ClearJob job{d_snp_counts.p, 4 * sizeof(uint64_t), 0};
         be.clear_many(&job, 1);
@@ -1806,7 +1807,7 @@ public:
         if (snp_rows < 2) { error = "no SNP collection has been started"; return -2; }
         if (snp_cols + n_cols >= ((int64_t)1 << 31)) { error = "a SNP collection takes fewer than 2^31 columns"; return -5; }
         timing.clear();
-        snp_dist_ready = false; boot_dist_ready = false;
+        snp_dist_ready = false; boot_dist_ready = false; rec_forget();
         const size_t n = (size_t)snp_rows, nc = (size_t)n_cols;
         uint64_t counts[4] = {0, 0, 0, 0};
         if (n_cols) {
@@ -2099,6 +2100,147 @@ public:
         return 0;
     }
 
+    // Recombination scan of the SNP collection (rec_kernels.h).  The transposed planes are made once per collection
+    // (any add forgets them) and stay on the device; so do the matrices of the last rec_incompat for rec_test.  Windows are worked off
+    // in batches: a launch takes at most kRecLaunchItems wavefronts, an upload of caller's matrices at most kRecUploadBytes
+    // ("rec_batch" forces the windows of a batch; no result depends on it: a window's keys come from its number g, not its place).
+    static constexpr size_t kRecMatrixBytes = (size_t)1 << 30, kRecUploadBytes = (size_t)256 << 20;
+    static constexpr int64_t kRecLaunchItems = (int64_t)1 << 30;
+    int64_t rec_batch = 0;      // pm_session_tune "rec_batch": windows per batch, 0: the largest that fits
+    bool rec_tp_ready = false, rec_inc_ready = false;      // the transposed planes / the matrices of rec_sizes are on the device
+    std::vector<int32_t> rec_sizes;                         // the sites of every window of those matrices
+    void rec_forget() { rec_tp_ready = false; rec_inc_ready = false; }
+    int32_t rec_row_blocks() const { return (snp_rows + 63) / 64; }
+    // queues RecTranspose and RecInform unless the planes of this collection are there already (phase rec_sites)
+    void rec_queue_sites() {
+        if (rec_tp_ready || !snp_v) return;
+        const int32_t RB = rec_row_blocks();
+        const int64_t words = (snp_v + 63) / 64;
+        ensure(d_rec_tp, (size_t)snp_v * 2 * (size_t)RB); ensure(d_rec_flag, (size_t)snp_v);
+        be.mark("rec_sites");
+        be.launch_wave("rec_transpose", words * RB, RecTranspose{d_snp_lo.p, d_snp_hi.p, snp_rows, snp_v, RB, d_rec_tp.p});
+        be.launch("rec_inform", snp_v, RecInform{d_rec_tp.p, snp_rows, RB, d_rec_flag.p});
+        be.mark(nullptr);
+        rec_tp_ready = true;
+    }
+    int rec_sites(uint8_t* informative, int64_t* n_informative) {
+        if (snp_rows < 2) { error = "no SNP collection has been started"; return -2; }
+        timing.clear();
+        int64_t count = 0;
+        if (snp_v) {
+            rec_queue_sites();
+            std::vector<uint8_t> own;
+            uint8_t* f = informative;
+            if (!f) { own.resize((size_t)snp_v); f = own.data(); }
+            be.d2h(f, d_rec_flag.p, (size_t)snp_v);
+            for (int64_t c = 0; c < snp_v; c++) count += f[c];
+        }
+        collect_timing_more();
+        if (n_informative) *n_informative = count;
+        return 0;
+    }
+    // the windows of a call: -2 / -5 with `error` set, or 0 with the sizes
+    int rec_windows_of(int64_t n_windows, const int64_t* win_off, int64_t n_sites, std::vector<int32_t>* sizes) {
+        if (n_windows < 0 || (n_windows && !win_off)) { error = "bad window list"; return -2; }
+        sizes->assign((size_t)n_windows, 0);
+        if (n_windows && (win_off[0] < 0 || (n_sites >= 0 && win_off[n_windows] > n_sites))) { error = "the windows lie outside the site list"; return -2; }
+        for (int64_t w = 0; w < n_windows; w++)
+            if (win_off[w + 1] - win_off[w] < 2) { error = "window " + std::to_string(w) + " has fewer than 2 sites (win_off must ascend)"; return -2; }
+        for (int64_t w = 0; w < n_windows; w++) {
+            if (win_off[w + 1] - win_off[w] > kRecMaxSites) { error = "a window takes at most " + std::to_string(kRecMaxSites) + " sites"; return -5; }
+            (*sizes)[(size_t)w] = (int32_t)(win_off[w + 1] - win_off[w]);
+        }
+        return 0;
+    }
+    static std::vector<int64_t> rec_matrix_offsets(const std::vector<int32_t>& sizes) {
+        std::vector<int64_t> off(sizes.size() + 1, 0);
+        for (size_t w = 0; w < sizes.size(); w++) off[w + 1] = off[w] + (int64_t)sizes[w] * sizes[w];
+        return off;
+    }
+    int rec_incompat(int64_t n_sites, const int64_t* sites, int64_t n_windows, const int64_t* win_off, uint8_t* inc_out) {
+        if (snp_rows < 2) { error = "no SNP collection has been started"; return -2; }
+        if (n_sites < 0 || (n_sites && !sites)) { error = "bad site list"; return -2; }
+        for (int64_t i = 0; i < n_sites; i++) if (sites[i] < 0 || sites[i] >= snp_v) { error = "site " + std::to_string(i) + " is no core SNP column of the collection"; return -2; }
+        std::vector<int32_t> sizes;
+        if (const int rc = rec_windows_of(n_windows, win_off, n_sites, &sizes)) return rc;
+        const std::vector<int64_t> moff = rec_matrix_offsets(sizes);
+        if ((size_t)moff.back() > kRecMatrixBytes) { error = "the matrices of the windows of one call do not fit"; return -5; }
+        timing.clear();
+        rec_inc_ready = false;
+        const size_t nw = (size_t)n_windows, total = (size_t)moff.back();
+        if (nw) {
+            ensure(d_rec_sites, (size_t)n_sites); ensure(d_rec_woff, nw + 1); ensure(d_rec_moff, nw + 1); ensure(d_rec_inc, total);
+            be.h2d(d_rec_sites.p, sites, 8 * (size_t)n_sites);
+            be.h2d(d_rec_woff.p, win_off, 8 * (nw + 1));
+            be.h2d(d_rec_moff.p, moff.data(), 8 * (nw + 1));
+            rec_queue_sites();
+            const size_t full = (size_t)((kRecMaxSites / kRecTile) * (kRecMaxSites / kRecTile));
+            const size_t batch = std::min(nw, rec_batch ? (size_t)rec_batch : (size_t)kRecLaunchItems / full);
+            be.mark("rec_incompat");
+            for (size_t b0 = 0; b0 < nw; b0 += batch) {
+                const size_t nb = std::min(batch, nw - b0);
+                int32_t kmax = 0;
+                for (size_t w = b0; w < b0 + nb; w++) kmax = std::max(kmax, sizes[w]);
+                const int32_t tiles = (kmax + kRecTile - 1) / kRecTile;
+                be.launch_wave("rec_incompat", (int64_t)nb * tiles * tiles,
+                               RecIncompat{d_rec_tp.p, snp_rows, rec_row_blocks(), d_rec_sites.p, d_rec_woff.p + b0, d_rec_moff.p + b0, tiles, d_rec_inc.p});
+            }
+            be.mark(nullptr);
+            if (inc_out) be.d2h_async(inc_out, d_rec_inc.p, total);
+            be.sync();
+            collect_timing_more();
+        }
+        rec_sizes.swap(sizes); rec_inc_ready = true;
+        return 0;
+    }
+    int rec_test(int64_t n_windows, const int64_t* win_off, const uint8_t* inc, int32_t near, int32_t perms, uint64_t seed, const int64_t* win_id,
+                 int32_t* phi, int32_t* le) {
+        if (near < 1) { error = "near must be at least 1"; return -2; }
+        if (perms < 1) { error = "a permutation test needs at least 1 permutation"; return -2; }
+        std::vector<int32_t> sizes;
+        if (const int rc = rec_windows_of(n_windows, win_off, -1, &sizes)) return rc;
+        if (perms > kRecMaxPerms) { error = "a permutation test takes at most " + std::to_string(kRecMaxPerms) + " permutations"; return -5; }
+        if (!inc && (!rec_inc_ready || sizes != rec_sizes)) { error = "no matrices of these windows are on the device"; return -2; }
+        if (n_windows && (!phi || !le)) { error = "bad argument"; return -2; }
+        const std::vector<int64_t> moff = rec_matrix_offsets(sizes);
+        if ((size_t)moff.back() > kRecMatrixBytes) { error = "the matrices of the windows of one call do not fit"; return -5; }
+        timing.clear();
+        const size_t nw = (size_t)n_windows, total = (size_t)moff.back();
+        if (!nw) return 0;
+        std::vector<int64_t> woff(nw + 1, 0);
+        for (size_t w = 0; w < nw; w++) woff[w + 1] = woff[w] + sizes[w];
+        ensure(d_rec_woff, nw + 1); ensure(d_rec_moff, nw + 1); ensure(d_rec_phi, nw); ensure(d_rec_le, nw);
+        if (inc) { rec_inc_ready = false; ensure(d_rec_inc, total); }
+        be.h2d(d_rec_woff.p, woff.data(), 8 * (nw + 1));
+        be.h2d(d_rec_moff.p, moff.data(), 8 * (nw + 1));
+        if (win_id) { ensure(d_rec_wid, nw); be.h2d(d_rec_wid.p, win_id, 8 * nw); }
+        ClearJob job{d_rec_le.p, nw * sizeof(uint32_t), 0};
+        be.clear_many(&job, 1);
+        const int32_t chunks = (perms + kRecChunk - 1) / kRecChunk;
+        size_t batch = std::min(nw, rec_batch ? (size_t)rec_batch : (size_t)(kRecLaunchItems / chunks));
+        for (size_t b0 = 0; b0 < nw; ) {
+            size_t nb = std::min(batch, nw - b0);
+            if (inc && !rec_batch)      // (a caller's matrices go up batch by batch)
+                while (nb > 1 && (size_t)(moff[b0 + nb] - moff[b0]) > kRecUploadBytes) nb--;
+            if (inc) be.h2d(d_rec_inc.p + moff[b0], inc + moff[b0], (size_t)(moff[b0 + nb] - moff[b0]));
+            int32_t kmax = 0;
+            for (size_t w = b0; w < b0 + nb; w++) kmax = std::max(kmax, sizes[w]);
+            const int64_t* wid = win_id ? d_rec_wid.p + b0 : nullptr;
+            be.mark("rec_permute");
+            if (kmax <= 128)
+                be.launch_wave("rec_permute", (int64_t)nb * chunks, RecPermute<128>{d_rec_inc.p, d_rec_woff.p + b0, d_rec_moff.p + b0, wid, (int64_t)b0, near, perms, chunks, seed, d_rec_phi.p + b0, d_rec_le.p + b0});
+            else
+                be.launch_wave("rec_permute", (int64_t)nb * chunks, RecPermute<256>{d_rec_inc.p, d_rec_woff.p + b0, d_rec_moff.p + b0, wid, (int64_t)b0, near, perms, chunks, seed, d_rec_phi.p + b0, d_rec_le.p + b0});
+            be.mark(nullptr);
+            b0 += nb;
+        }
+        be.d2h_async(phi, d_rec_phi.p, 4 * nw); be.d2h_async(le, d_rec_le.p, 4 * nw);
+        be.sync();
+        collect_timing_more();
+        if (inc) { rec_sizes.swap(sizes); rec_inc_ready = true; }
+        return 0;
+    }
+
     // The suffix array of the flagged regions of a batch (dense_kernels.h) and their rep' (after RepeatLength, which skipped them).
     // One segmented prefix-doubling sort over all of them; every round waits for its count of distinct ranks (8 bytes) -- a round
     // trip per round, on this path only.
@@ -2226,6 +2368,7 @@ public:
         if (key == "hint_shrink" && value >= 1) { hint_shrink = value; return true; }
         if (key == "copy_kernel") { return tune_copy_kernel(be, value != 0, 0); }
         if (key == "boot_batch" && value >= 0) { boot_batch = value; return true; }
+        if (key == "rec_batch" && value >= 0) { rec_batch = value; return true; }
         return false;
     }
 
@@ -2319,6 +2462,8 @@ private:
     // the bootstrap (boot_kernels.h): draw counters, weights as bytes and planes, replicate distances; the trees of a batch; splits and support
     Buf<uint32_t> d_boot_cnt, d_bs_support; Buf<uint8_t> d_boot_w8, d_bt_active; Buf<uint64_t> d_boot_planes, d_bs_msets, d_bs_mkeys, d_bs_rsets, d_bs_rkeys;
     Buf<int32_t> d_boot_dist, d_bt_dist, d_bt_j; Buf<double> d_bt_D, d_bt_R, d_bt_q; Buf<NjJoinRec> d_bt_joins, d_bs_mj, d_bs_rj; Buf<NjLastRec> d_bt_last;
+    // the recombination scan (rec_kernels.h): transposed planes, informative flags; sites, window and matrix offsets, window numbers; matrices, phi, le
+    Buf<uint64_t> d_rec_tp; Buf<uint8_t> d_rec_flag, d_rec_inc; Buf<int64_t> d_rec_sites, d_rec_woff, d_rec_moff, d_rec_wid; Buf<int32_t> d_rec_phi; Buf<uint32_t> d_rec_le;
     Buf<uint64_t> d_snp_counts, d_snp_lo, d_snp_hi; Buf<uint8_t> d_snp_chunk; Buf<int64_t> d_snp_flag, d_snp_rank, d_snp_col; Buf<int32_t> d_snp_dist;      // the SNP collection (snp_kernels.h)
     Buf<uint8_t> d_ms_strand, d_ms_state, d_small8, d_o_strand; Buf<int32_t> d_ms_shift, d_ms_len, d_list, d_list2, d_j_min, d_j_max, d_o_start;
     Buf<int64_t> d_rg_start, d_rg_len, d_lay_off, d_lay_bits, d_v_row0, d_v_first, d_f_start, d_f_end, d_f_pack; Buf<RegInfo> d_rg_info; Buf<uint64_t> d_rg_count, d_once, d_twice;

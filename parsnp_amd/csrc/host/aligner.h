@@ -51,6 +51,9 @@ struct Params {
     bool snps = false;      // [Output] snps: core SNP columns and SNP distances beside the XMFA (snps.cpp); the reference ignores the key
     int bootstrap = 0;      // [Output] bootstrap=B: B bootstrap replicates label the tree's branches with their support (tree.cpp); implies tree
     uint64_t bootseed = 1;  // [Output] bootseed: the seed of the replicates' draws
+    bool recomb = false;    // [Output] recomb: the recombination scan of the core SNP columns beside them (recomb.cpp); implies snps
+    int recperms = 1000, recsites = 100, recnear = 10;      // [Output] recperms, recsites, recnear: permutations, sites of a window, H
+    uint64_t recseed = 1;   // [Output] recseed: the seed of the permutations
     bool tree = false;      // [Output] tree: the neighbour-joining tree of the SNP distances beside them (tree.cpp); implies snps
     float diag_diff = 1.0f, factor = 0.0f;
     std::string anchors, mums, anchorfile, mumfile, prefix, outdir;
@@ -534,7 +537,9 @@ public:
     // the three files beside the XMFA, the console line, snp_counts
     // (tree: then the neighbour-joining tree of the distances, which are still on the device -- tree.cpp)
     // (bootstrap > 0: then the tree once more with the support of bootstrap replicates on its branches)
-    void finish(const std::vector<Genome>& genomes, const std::string& dir, const std::string& stem, bool tree = false, int bootstrap = 0, uint64_t bootseed = 1);
+    // (rec: then the recombination scan of the columns, which are still on the device -- recomb.cpp)
+    void finish(const std::vector<Genome>& genomes, const std::string& dir, const std::string& stem, bool tree = false, int bootstrap = 0, uint64_t bootseed = 1,
+                const struct RecParams* rec = nullptr);
 
 private:
     struct Entry { int64_t first; int32_t cluster; int32_t width; int64_t c0; };      // columns [first, first + width) of all columns handed over
@@ -560,6 +565,24 @@ std::string nj_newick(const std::vector<std::string>& names, const pm_nj_join* j
 // bootstrap > 0: then <stem>.snps.boot.nwk, the same text with the support of join t behind its node
 void write_tree(pm_session* session, const std::vector<std::string>& names, const int32_t* dist, const std::string& dir, const std::string& stem,
                 int bootstrap = 0, uint64_t bootseed = 1);
+
+// The recombination scan of the core SNP columns ([Output] recomb=1; recomb.cpp): the engine flags the informative
+// columns, scores the pairs of sites of every window and tests every window against its permutations (pm_rec_*); the host cuts the
+// LCBs' site lists into windows and writes <stem>.rec.tsv and <stem>.rec.
+struct RecParams { int perms = 1000; uint64_t seed = 1; int sites = 100; int near = 10; };
+struct RecCounts { bool on = false; long sites = 0, windows = 0, flagged = 0; double ms = 0; };
+extern RecCounts rec_counts;        // what the last write_output scanned (PARSNP_TIMING: rec_*, with recomb=1 only)
+constexpr size_t kRecMinSites = 16; // an LCB with fewer informative sites has no window
+struct RecColumn { int32_t cluster; int64_t column, ref_pos; };      // a core SNP column as <stem>.snps.tsv prints it
+struct RecWindow { int32_t cluster; int64_t first_column, last_column, first_ref, last_ref; int32_t sites; };
+void rec_limits(int* rows, int* sites, int* perms);      // sequences, recsites and recperms a run with recomb=1 may have
+std::vector<size_t> rec_window_starts(size_t m, size_t K);
+// the windows in order g over the informative columns of every LCB; sites / win_off: what pm_rec_incompat takes
+std::vector<RecWindow> rec_windows(const std::vector<RecColumn>& cols, const uint8_t* informative, size_t K, std::vector<int64_t>* sites, std::vector<int64_t>* win_off);
+bool rec_flagged(int32_t le, int32_t perms);
+std::string rec_tsv_text(const std::vector<RecWindow>& win, const int32_t* phi, const int32_t* le, int32_t perms);
+std::string rec_bed_text(const std::vector<RecWindow>& win, const int32_t* le, int32_t perms, long* flagged);
+void write_recomb(pm_session* session, const std::vector<RecColumn>& cols, const RecParams& prm, const std::string& dir, const std::string& stem);
 
 std::string reverse_complement(const std::string& s);   // Aligner::reversec, :1294-1393
 

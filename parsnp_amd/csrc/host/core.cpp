@@ -51,6 +51,12 @@ int CoreRun::open(const std::string& ini_path) {
     prm.bootseed = strtoull(ini.get("Output", "bootseed", "1").c_str(), nullptr, 10);
     if (prm.bootstrap > 0) prm.tree = true;      // (the support values label the branches of the tree)
     if (prm.tree) prm.snps = true;      // (the tree is built over the SNP distances)
+    prm.recomb = ini.get_bool("Output", "recomb");
+    prm.recperms = atoi(ini.get("Output", "recperms", "1000").c_str());
+    prm.recsites = atoi(ini.get("Output", "recsites", "100").c_str());
+    prm.recnear = atoi(ini.get("Output", "recnear", "10").c_str());
+    prm.recseed = strtoull(ini.get("Output", "recseed", "1").c_str(), nullptr, 10);
+    if (prm.recomb) prm.snps = true;    // (the scan reads the core SNP columns)
     const bool reverse_ref = ini.get_bool("Reference", "reverse");
     qfiles = (int)ini.count("Query") / 2;
 
@@ -71,6 +77,18 @@ int CoreRun::open(const std::string& ini_path) {
     if (prm.bootstrap > boot_max_reps()) {
         std::cerr << "parsnp_core: input exceeds a limit of the multi-MUM engine: bootstrap takes at most " << boot_max_reps() << " replicates" << std::endl;
         return 5;
+    }
+
+    if (prm.recomb) {
+        int rows = 0, sites = 0, perms = 0;
+        rec_limits(&rows, &sites, &perms);
+        const char* what = qfiles + 1 > rows ? "sequences" : prm.recperms < 1 || prm.recperms > perms ? "recperms" : prm.recsites < (int)kRecMinSites || prm.recsites > sites ? "recsites"
+                           : prm.recnear < 1 ? "recnear" : nullptr;
+        if (what) {
+            std::cerr << "parsnp_core: input exceeds a limit of the multi-MUM engine: recomb=1 takes at most " << rows << " sequences, 1 <= recperms <= " << perms
+                      << ", " << kRecMinSites << " <= recsites <= " << sites << ", recnear >= 1 (" << what << ")" << std::endl;
+            return 5;
+        }
     }
 
     time_t start, end;

@@ -169,6 +169,9 @@ int main(int argc, char* argv[]) {
                 fprintf(f, ", \"nj_ms\": %.3f, \"nj_joins\": %ld", tree_counts.nj_ms, tree_counts.joins);
             if (tree_counts.boot_on)      // (bootstrap=B only)
                 fprintf(f, ", \"boot_reps\": %ld, \"boot_ms\": %.3f", tree_counts.boot_reps, tree_counts.boot_ms);
+            if (rec_counts.on)      // (recomb=1 only)
+                fprintf(f, ", \"rec_sites\": %ld, \"rec_windows\": %ld, \"rec_flagged\": %ld, \"rec_ms\": %.3f", rec_counts.sites, rec_counts.windows,
+                        rec_counts.flagged, rec_counts.ms);
             fprintf(f, "}\n");
             fclose(f);
         }

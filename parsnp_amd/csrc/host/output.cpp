@@ -916,7 +916,9 @@ void write_output(Aligner& a, const std::string& stem, bool* gap_note) {
 
     lap("xmfa records");
     tree_counts = TreeCounts();
-    if (snp) { snp->finish(a.genomes, dir, stem, prm.tree, prm.bootstrap, prm.bootseed); lap("snp columns"); }
+    rec_counts = RecCounts();
+    const RecParams rec_prm{prm.recperms, prm.recseed, prm.recsites, prm.recnear};
+    if (snp) { snp->finish(a.genomes, dir, stem, prm.tree, prm.bootstrap, prm.bootseed, prm.recomb ? &rec_prm : nullptr); lap("snp columns"); }
     // ---- log (:1082-1190); stream flags are sticky exactly as in the reference
     log << "Number of sequences analyzed:" << setiosflags(ios::fixed) << setprecision(1) << setw(10) << n << endl << endl;
     for (size_t i = 0; i < n; i++) {

@@ -96,12 +96,14 @@ void SnpCollector::flush() {
     used_ = 0;
 }
 
-void SnpCollector::finish(const std::vector<Genome>& genomes, const std::string& dir, const std::string& stem, bool tree, int bootstrap, uint64_t bootseed) {
+void SnpCollector::finish(const std::vector<Genome>& genomes, const std::string& dir, const std::string& stem, bool tree, int bootstrap, uint64_t bootseed,
+                          const RecParams* rec) {
     flush();
     const size_t v = (size_t)counts_.core_snps;
     std::vector<int64_t> col(v);
     std::vector<uint8_t> letters(n_ * v);
     std::vector<int32_t> dist(n_ * n_);
+    std::vector<RecColumn> rec_cols;      // (recomb=1: what the .snps.tsv says of every core SNP column)
     int rc = pm_snp_columns(session_, col.data(), letters.data());
     if (rc != PM_OK) snp_fatal("cannot fetch the SNP columns", rc);
     rc = pm_snp_distances(session_, dist.data());
@@ -123,11 +125,13 @@ void SnpCollector::finish(const std::vector<Genome>& genomes, const std::string&
     {
         std::ofstream tsv((dir + stem + ".snps.tsv").c_str(), std::ios::binary);
         tsv << "cluster\tcolumn\tref_pos\n";
+        if (rec) rec_cols.reserve(v);
         size_t e = 0;      // (col ascends: the entries are walked once)
         for (size_t k = 0; k < v; k++) {
             while (e + 1 < entries_.size() && entries_[e + 1].first <= col[k]) e++;
             const Entry& en = entries_[e];
             tsv << en.cluster << '\t' << en.c0 + (col[k] - en.first) << '\t' << ref_pos_[(size_t)col[k]] << '\n';
+            if (rec) rec_cols.push_back(RecColumn{en.cluster, en.c0 + (col[k] - en.first), ref_pos_[(size_t)col[k]]});
         }
     }
     {
@@ -148,6 +152,7 @@ void SnpCollector::finish(const std::vector<Genome>& genomes, const std::string&
         for (size_t i = 0; i < n_; i++) names.push_back(genomes[i].fname);
         write_tree(session_, names, dist.data(), dir, stem, bootstrap, bootseed);
     }
+    if (rec) write_recomb(session_, rec_cols, *rec, dir, stem);      // (the collection is still on the device; the tree does not touch it)
     snp_counts.on = true;
     snp_counts.columns = (long)counts_.columns + invariant_; snp_counts.invariant = (long)counts_.core_invariant + invariant_;
     snp_counts.core = (long)counts_.core_snps; snp_counts.other = (long)counts_.other;

@@ -51,12 +51,13 @@ def driver_order(paths):
     return out
 
 
-def ini_text(ref, queries, outdir, snps=None, tree=None, bootstrap=None, bootseed=None, **kw):
+def ini_text(ref, queries, outdir, snps=None, tree=None, bootstrap=None, bootseed=None, recomb=None, recperms=None, recseed=None, recsites=None, recnear=None, **kw):
     """snps=1: `snps=1` under [Output] (core SNP columns and SNP distances beside the XMFA: read_snps; the reference ignores the
     key).  tree=1: `tree=1` there (it implies snps=1: the neighbour-joining tree of the SNP distances, read_tree).  bootstrap=B:
     `bootstrap=B` there (it implies tree=1: the tree once more with the support of B bootstrap replicates on its branches,
-    read_boot_tree); bootseed=S: the seed of the replicates (default 1).  Without the arguments the text is the reference
-    driver's, byte for byte."""
+    read_boot_tree); bootseed=S: the seed of the replicates (default 1).  recomb=1: `recomb=1` there (it implies snps=1: the
+    recombination scan of the core SNP columns, read_rec), with recperms=P permutations (default 1000), recseed=S (1), recsites=K
+    sites a window (100) and recnear=H (10).  Without the arguments the text is the reference driver's, byte for byte."""
     p = dict(DEFAULTS, **kw)
     files = "".join("file%d=%s\nreverse%d=0\n" % (i, q, i) for i, q in enumerate(queries, 1))
     text = _TEMPLATE.format(ref=ref, files=files, outdir=outdir, **p)
@@ -68,6 +69,9 @@ def ini_text(ref, queries, outdir, snps=None, tree=None, bootstrap=None, bootsee
         text += "bootstrap=%d\n" % int(bootstrap)
     if bootseed is not None:
         text += "bootseed=%d\n" % int(bootseed)
+    for key, value in (("recomb", recomb), ("recperms", recperms), ("recseed", recseed), ("recsites", recsites), ("recnear", recnear)):
+        if value is not None:
+            text += "%s=%d\n" % (key, int(value))
     return text
 
 
@@ -130,3 +134,19 @@ def read_boot_tree(outdir, stem="parsnpAligner"):
     text = open(os.path.join(outdir, stem + ".snps.boot.nwk")).read()
     assert text.endswith(";\n") and text.count("\n") == 1
     return text[:-1]
+
+
+def read_rec(outdir, stem="parsnpAligner"):
+    """the two files a run with recomb=1 leaves beside the SNP files -> (rows, bed): rows = a dict per window of .rec.tsv in order g
+    (cluster, first_column, last_column, first_ref, last_ref, sites, phi, le, perms as int, p as printed), bed = the lines of .rec
+    (the upstream driver's parsnp.rec: a record per flagged window) without their newlines"""
+    lines = open(os.path.join(outdir, stem + ".rec.tsv")).read().split("\n")
+    head = lines[0].split("\t")
+    assert head == ["cluster", "first_column", "last_column", "first_ref", "last_ref", "sites", "phi", "le", "perms", "p"] and lines[-1] == ""
+    rows = []
+    for line in lines[1:-1]:
+        f = line.split("\t")
+        rows.append(dict(zip(head, [int(x) for x in f[:-1]] + [f[-1]])))
+    bed = open(os.path.join(outdir, stem + ".rec")).read().split("\n")
+    assert bed[-1] == ""
+    return rows, bed[:-1]
