@@ -415,6 +415,34 @@ int pm_rec_sites(pm_session* s, uint8_t* informative, int64_t* n_informative);
 int pm_rec_incompat(pm_session* s, int64_t n_sites, const int64_t* sites, int64_t n_windows, const int64_t* win_off, uint8_t* inc_out);
 int pm_rec_test(pm_session* s, int64_t n_windows, const int64_t* win_off, const uint8_t* inc, int32_t near, int32_t perms, uint64_t seed,
                 const int64_t* win_id, int32_t* phi, int32_t* le);
+/* Extension of LCB ends into their flanks (DEFINED in INTEGRATION.md 1e; all integers, exact): a banded alignment of every row's
+ * flank against the reference's, a cut common to the rows of a job, the paths and their star merge into columns.  The limits call
+ * reports the rows of a job (2 048), the longest flank (512) and the widest band (63); it needs no device.
+ * A row is a descriptor into the session's resident genomes: letter q (0 <= q < len) is base first + q step (0-based) of the forward
+ * strand of `genome`, complemented where `complement` is 1.  A row may name any genome, any number of times.  The rows of job j are
+ * rows[row_off[j]] ... rows[row_off[j + 1] - 1] (row_off[0] = 0), the first of them the reference row.  A base that is none of ACGT
+ * matches nothing and prints as N.
+ * pm_ext_reach: reach[j] = the job's reach A of 1e (0: dropped).  best: NULL, or for every row (max_flank + 1) int32, best_r(i) for
+ * i = 0 ... La and INT32_MIN where it is undefined or i > La (the reference row is aligned with itself like any other).  Phases
+ * `ext_reach`, `ext_cut`.
+ * pm_ext_align: for the reaches given (those of pm_ext_reach, or any 0 <= reach[j] <= La at which every row of the job has a cell:
+ * reach[j] <= len + band for each of its rows; another is PM_EINVAL): used[p] = j_r of every row (0 in a job
+ * of reach 0), cols[j] = the job's columns C, 0 for reach 0, -1 where C > 2 max_flank (no letters are written then).  Every byte of
+ * the n_j x max_cols block of a job that holds no letter is written as 0.  The row r of job j
+ * is written to out_rows + out_off[j] + r max_cols, C letters of ACGTN- in the flank's own order (the column next to the LCB first;
+ * a caller that prints a left flank reverses it).  max_cols >= 2 max_flank.  Phases `ext_trace`, `ext_merge`.
+ * PM_EINVAL: a parameter outside its range (16 <= max_flank <= 512, 1 <= band <= 63, 1 <= match <= 15, 0 <= mismatch <= 15,
+ * 1 <= gap <= 15, 50 <= ani <= 100, 1 <= min_len <= max_flank), a job of fewer than 2 rows, a row_off that does not ascend from 0,
+ * a step other than +1 / -1, a len < 0, a descriptor that leaves its genome, a reach outside 0 ... La, max_cols too small.
+ * PM_ELIMIT: a len > max_flank, a job of more than 2 048 rows, 2^31 rows or jobs in a call.  n_jobs == 0 is valid and launches nothing.  The
+ * pairs are worked off in batches; pm_session_tune(s, "ext_batch", k) forces k pairs a launch (0: the default); no result depends
+ * on k. */
+typedef struct pm_ext_params { int32_t match, mismatch, gap, band, ani, min_len, max_flank; } pm_ext_params;
+typedef struct pm_ext_row { int32_t genome, step, complement, len; int64_t first; } pm_ext_row;
+int pm_ext_limits(int* max_rows, int* max_flank, int* max_band);
+int pm_ext_reach(pm_session* s, const pm_ext_params* params, int64_t n_jobs, const int64_t* row_off, const pm_ext_row* rows, int32_t* reach, int32_t* best);
+int pm_ext_align(pm_session* s, const pm_ext_params* params, int64_t n_jobs, const int64_t* row_off, const pm_ext_row* rows, const int32_t* reach,
+                 int64_t max_cols, const int64_t* out_off, uint8_t* out_rows, int32_t* cols, int32_t* used);
 /* bytes this session has moved over the host link so far (every copy the engine issued, both directions) */
 int pm_session_traffic(const pm_session* s, uint64_t* h2d_bytes, uint64_t* d2h_bytes);
 

@@ -99,6 +99,10 @@ class Lib:
         pm_rec_limits"""
         return self._gap_limits_of("pm_rec_limits")
 
+    def ext_limits(self):
+        """(rows of a job, longest flank, widest band) of the LCB extension (Session.ext_reach, ext_align): pm_ext_limits"""
+        return self._gap_limits_of("pm_ext_limits")
+
     def _gap_limits_of(self, name):
         if not hasattr(self.L, name):
             raise PmError("this provider of the ABI has no %s" % name)
@@ -360,6 +364,58 @@ class Session:
         self.lib._check(fn(self.h, nw, win_off.ctypes.data_as(v), inc.ctypes.data_as(v) if inc is not None else None, near, perms, seed & (2 ** 64 - 1),
                            win_id.ctypes.data_as(v) if win_id is not None else None, phi.ctypes.data_as(v), le.ctypes.data_as(v)))
         return phi, le
+
+    EXT_ROW = np.dtype([("genome", np.int32), ("step", np.int32), ("complement", np.int32), ("len", np.int32), ("first", np.int64)])
+    EXT_DEFAULTS = dict(match=5, mismatch=4, gap=2, band=50, ani=95, min_len=10, max_flank=256)
+
+    @classmethod
+    def _ext_args(cls, params, row_off, rows):
+        p = dict(cls.EXT_DEFAULTS, **(params or {}))
+        prm = np.array([p[k] for k in ("match", "mismatch", "gap", "band", "ani", "min_len", "max_flank")], np.int32)
+        row_off = np.ascontiguousarray(row_off, np.int64)
+        assert row_off.ndim == 1 and len(row_off) >= 1
+        if not (isinstance(rows, np.ndarray) and rows.dtype == cls.EXT_ROW):
+            rows = np.array([tuple(r) for r in rows], cls.EXT_ROW)      # (genome, step, complement, len, first) per row
+        rows = np.ascontiguousarray(rows)
+        assert len(rows) >= row_off[-1]
+        return p, prm, row_off, rows, len(row_off) - 1
+
+    def ext_reach(self, row_off, rows, params=None, best=False):
+        """pm_ext_reach -> reach, int32 [jobs]: the rows of job j are rows[row_off[j]:row_off[j + 1]], tuples
+        (genome, step, complement, len, first) or a record array of EXT_ROW, the first of a job its reference row.  params: a dict
+        over EXT_DEFAULTS.  best=True: -> (reach, best), best int32 [rows, max_flank + 1] with INT32_MIN where undefined."""
+        v = C.c_void_p
+        fn = self._rec_fn("pm_ext_reach", [v, v, C.c_int64, v, v, v, v])
+        p, prm, row_off, rows, nj = self._ext_args(params, row_off, rows)
+        reach = np.zeros(nj, np.int32)
+        table = np.zeros((len(rows), max(int(p["max_flank"]), 0) + 1), np.int32) if best else None
+        self.lib._check(fn(self.h, prm.ctypes.data_as(v), nj, row_off.ctypes.data_as(v), rows.ctypes.data_as(v), reach.ctypes.data_as(v),
+                           table.ctypes.data_as(v) if best else None))
+        return (reach, table) if best else reach
+
+    def ext_align(self, row_off, rows, reach, params=None, max_cols=None, out_off=None, out=None):
+        """pm_ext_align -> (cols, used, blocks): cols int32 [jobs] (0: reach 0, -1: too wide), used int32 [rows] (j_r), blocks a list
+        per job of uint8 [rows of the job, cols] (None where cols <= 0), the letters in the flank's own order.  max_cols: the pitch
+        of a row (default 2 max_flank); out_off: the byte offsets of the jobs' blocks (default: one after the other); out: the caller's
+        own uint8 buffer for the blocks (it must hold them all; the blocks returned are views of it)."""
+        v = C.c_void_p
+        fn = self._rec_fn("pm_ext_align", [v, v, C.c_int64, v, v, v, C.c_int64, v, v, v, v])
+        p, prm, row_off, rows, nj = self._ext_args(params, row_off, rows)
+        reach = np.ascontiguousarray(reach, np.int32)
+        assert reach.shape == (nj,)
+        pitch = 2 * int(p["max_flank"]) if max_cols is None else int(max_cols)
+        out_off = np.ascontiguousarray(row_off[:-1] * pitch if out_off is None else out_off, np.int64)
+        assert out_off.shape == (nj,)
+        n = np.diff(row_off)
+        size = int((out_off + n * pitch).max()) if nj and pitch > 0 and bool((n >= 0).all()) and bool((out_off >= 0).all()) else 0
+        if out is None:
+            out = np.zeros(size, np.uint8)
+        assert out.dtype == np.uint8 and out.ndim == 1 and out.flags.c_contiguous and len(out) >= size
+        cols, used = np.zeros(nj, np.int32), np.zeros(len(rows), np.int32)
+        self.lib._check(fn(self.h, prm.ctypes.data_as(v), nj, row_off.ctypes.data_as(v), rows.ctypes.data_as(v), reach.ctypes.data_as(v), pitch,
+                           out_off.ctypes.data_as(v), out.ctypes.data_as(v), cols.ctypes.data_as(v), used.ctypes.data_as(v)))
+        blocks = [out[out_off[j]:out_off[j] + n[j] * pitch].reshape(int(n[j]), pitch)[:, :cols[j]] if cols[j] > 0 else None for j in range(nj)]
+        return cols, used, blocks
 
     def __enter__(self):
         return self

@@ -351,6 +351,23 @@ int pm_rec_test(pm_session* s, int64_t n_windows, const int64_t* win_off, const 
     if (!s) return fail(PM_EINVAL, "bad argument");
     PM_STORE_CALL(s->engine->rec_test(n_windows, win_off, inc, near, perms, seed, win_id, phi, le))
 }
+// extension of the LCB ends (ext_kernels.h)
+static_assert(sizeof(pm_ext_row) == sizeof(pm::ExtRow) && sizeof(pm_ext_params) == sizeof(pm::ExtParams), "the ABI's records are the engine's");
+int pm_ext_limits(int* max_rows, int* max_flank, int* max_band) {
+    if (max_rows) *max_rows = pm::kExtMaxRows;
+    if (max_flank) *max_flank = pm::kExtMaxFlank;
+    if (max_band) *max_band = pm::kExtMaxBand;
+    return PM_OK;
+}
+int pm_ext_reach(pm_session* s, const pm_ext_params* params, int64_t n_jobs, const int64_t* row_off, const pm_ext_row* rows, int32_t* reach, int32_t* best) {
+    if (!s || !params) return fail(PM_EINVAL, "bad argument");
+    PM_STORE_CALL(s->engine->ext_reach(*(const pm::ExtParams*)params, n_jobs, row_off, (const pm::ExtRow*)rows, reach, best))
+}
+int pm_ext_align(pm_session* s, const pm_ext_params* params, int64_t n_jobs, const int64_t* row_off, const pm_ext_row* rows, const int32_t* reach,
+                 int64_t max_cols, const int64_t* out_off, uint8_t* out_rows, int32_t* cols, int32_t* used) {
+    if (!s || !params) return fail(PM_EINVAL, "bad argument");
+    PM_STORE_CALL(s->engine->ext_align(*(const pm::ExtParams*)params, n_jobs, row_off, (const pm::ExtRow*)rows, reach, max_cols, out_off, out_rows, cols, used))
+}
 int pm_session_traffic(const pm_session* s, uint64_t* h2d_bytes, uint64_t* d2h_bytes) {
     if (!s) return PM_EINVAL;
     if (h2d_bytes) *h2d_bytes = s->backend->bytes_h2d;

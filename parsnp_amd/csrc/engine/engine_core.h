@@ -32,6 +32,7 @@
 #include "nj_kernels.h"
 #include "boot_kernels.h"
 #include "rec_kernels.h"
+#include "ext_kernels.h"
 
 namespace pm {
 
@@ -2241,6 +2242,123 @@ public:
         return 0;
     }
 
+    // Extension of the LCB ends into their flanks (ext_kernels.h).  A pair is a (job, row): pair p is row p of the
+    // call's list.  The reach goes pair by pair in launches of at most `ext_batch` pairs (a job's pairs may straddle launches: the cut
+    // runs after the last); the alignment goes in batches of whole jobs of about as many pairs, whose paths and column starts stay in
+    // a workspace of the batch's size.  Only descriptors go up; reaches, `best` (for the tests), `used` and the rows come back.
+    static constexpr int64_t kExtBatchPairs = 1 << 16;
+    int64_t ext_batch = 0;      // pm_session_tune "ext_batch": pairs per launch, 0: kExtBatchPairs
+    // the jobs of a call: -2 / -5 with `error` set, or 0 with the job of every pair
+    int ext_check(const ExtParams& prm, int64_t n_jobs, const int64_t* row_off, const ExtRow* rows, std::vector<int32_t>* row_job) {
+        if (prm.max_flank < 16 || prm.max_flank > kExtMaxFlank || prm.band < 1 || prm.band > kExtMaxBand || prm.match < 1 || prm.match > 15 || prm.mismatch < 0 ||
+            prm.mismatch > 15 || prm.gap < 1 || prm.gap > 15 || prm.ani < 50 || prm.ani > 100 || prm.min_len < 1 || prm.min_len > prm.max_flank) {
+            error = "extension parameters out of range (16 <= max_flank <= 512, 1 <= band <= 63, 1 <= match <= 15, 0 <= mismatch <= 15, 1 <= gap <= 15, "
+                    "50 <= ani <= 100, 1 <= min_len <= max_flank)";
+            return -2;
+        }
+        if (n_jobs < 0 || !row_off || (n_jobs && !rows) || row_off[0] != 0) { error = "bad job list"; return -2; }
+        for (int64_t j = 0; j < n_jobs; j++)
+            if (row_off[j + 1] - row_off[j] < 2) { error = "job " + std::to_string(j) + " has fewer than 2 rows (row_off must ascend)"; return -2; }
+        if (n_jobs >= ((int64_t)1 << 31) || row_off[n_jobs] >= ((int64_t)1 << 31)) { error = "too many jobs or rows in one call"; return -5; }
+        for (int64_t j = 0; j < n_jobs; j++)
+            if (row_off[j + 1] - row_off[j] > kExtMaxRows) { error = "a job takes at most " + std::to_string(kExtMaxRows) + " rows"; return -5; }
+        row_job->assign((size_t)row_off[n_jobs], 0);
+        for (int64_t j = 0; j < n_jobs; j++)
+            for (int64_t p = row_off[j]; p < row_off[j + 1]; p++) {
+                const ExtRow& r = rows[p];
+                (*row_job)[(size_t)p] = (int32_t)j;
+                if (r.genome < 0 || r.genome >= ngen || (r.step != 1 && r.step != -1) || r.len < 0 || (r.complement != 0 && r.complement != 1)) { error = "row " + std::to_string(p) + ": bad descriptor"; return -2; }
+                if (r.len > prm.max_flank) { error = "row " + std::to_string(p) + " is longer than max_flank"; return -5; }
+                const int64_t end = r.first + (int64_t)(r.len - 1) * r.step;
+                if (r.len && (r.first < 0 || r.first >= glen_h[(size_t)r.genome] || end < 0 || end >= glen_h[(size_t)r.genome])) { error = "row " + std::to_string(p) + " leaves its genome"; return -2; }
+            }
+        return 0;
+    }
+    void ext_upload(int64_t n_jobs, const int64_t* row_off, const ExtRow* rows, const std::vector<int32_t>& row_job) {
+        const size_t np = row_job.size();
+        ensure(d_ext_rows, np); ensure(d_ext_job, np); ensure(d_ext_off, (size_t)n_jobs + 1);
+        be.h2d(d_ext_rows.p, rows, sizeof(ExtRow) * np);
+        be.h2d(d_ext_job.p, row_job.data(), 4 * np);
+        be.h2d(d_ext_off.p, row_off, 8 * ((size_t)n_jobs + 1));
+    }
+    int ext_reach(const ExtParams& prm, int64_t n_jobs, const int64_t* row_off, const ExtRow* rows, int32_t* reach, int32_t* best) {
+        std::vector<int32_t> row_job;
+        if (const int rc = ext_check(prm, n_jobs, row_off, rows, &row_job)) return rc;
+        if (n_jobs && !reach) { error = "bad argument"; return -2; }
+        timing.clear();
+        if (!n_jobs) return 0;
+        const int64_t np = (int64_t)row_job.size(), pitch = prm.max_flank + 1;
+        const int64_t batch = ext_batch ? ext_batch : kExtBatchPairs;
+        ext_upload(n_jobs, row_off, rows, row_job);
+        ensure(d_ext_bits, (size_t)np * kExtBitWords); ensure(d_ext_reach, (size_t)n_jobs);
+        if (best) ensure(d_ext_best, (size_t)std::min(batch, np) * (size_t)pitch);
+        for (int64_t p0 = 0; p0 < np; p0 += batch) {
+            const int64_t nb = std::min(batch, np - p0);
+            be.mark("ext_reach");
+            be.launch_wave("ext_reach", nb, ExtReach{P, d_ext_rows.p, d_ext_job.p, d_ext_off.p, prm, p0, d_ext_bits.p, best ? d_ext_best.p : nullptr});
+            be.mark(nullptr);
+            if (best) be.d2h(best + p0 * pitch, d_ext_best.p, 4 * (size_t)(nb * pitch));
+        }
+        be.mark("ext_cut");
+        be.launch_wave("ext_cut", n_jobs, ExtCut{d_ext_off.p, prm, d_ext_bits.p, d_ext_reach.p});
+        be.mark(nullptr);
+        be.d2h_async(reach, d_ext_reach.p, 4 * (size_t)n_jobs);
+        be.sync();
+        collect_timing_more();
+        return 0;
+    }
+    int ext_align(const ExtParams& prm, int64_t n_jobs, const int64_t* row_off, const ExtRow* rows, const int32_t* reach, int64_t max_cols, const int64_t* out_off,
+                  uint8_t* out_rows, int32_t* cols, int32_t* used) {
+        std::vector<int32_t> row_job;
+        if (const int rc = ext_check(prm, n_jobs, row_off, rows, &row_job)) return rc;
+        if (n_jobs && (!reach || !out_off || !out_rows || !cols || !used)) { error = "bad argument"; return -2; }
+        if (max_cols < 2 * (int64_t)prm.max_flank) { error = "max_cols must be at least 2 max_flank"; return -2; }
+        for (int64_t j = 0; j < n_jobs; j++) {
+            if (reach[j] < 0 || reach[j] > rows[row_off[j]].len) { error = "job " + std::to_string(j) + ": the reach lies outside the reference flank"; return -2; }
+            for (int64_t p = row_off[j]; p < row_off[j + 1]; p++)      // (line A of a row's table has a cell only up to len + band)
+                if (reach[j] > rows[p].len + prm.band) { error = "job " + std::to_string(j) + ": line " + std::to_string(reach[j]) + " of row " + std::to_string(p) + " has no cell"; return -2; }
+            if (out_off[j] < 0) { error = "bad output offset"; return -2; }
+        }
+        timing.clear();
+        if (!n_jobs) return 0;
+        const int64_t np = (int64_t)row_job.size();
+        const int64_t batch = ext_batch ? ext_batch : kExtBatchPairs;
+        ext_upload(n_jobs, row_off, rows, row_job);
+        ensure(d_ext_reach, (size_t)n_jobs); ensure(d_ext_cols, (size_t)n_jobs); ensure(d_ext_used, (size_t)np);
+        be.h2d(d_ext_reach.p, reach, 4 * (size_t)n_jobs);
+        std::vector<uint8_t> stage;
+        for (int64_t j0 = 0; j0 < n_jobs; ) {      // whole jobs, about `batch` pairs
+            int64_t j1 = j0 + 1;
+            while (j1 < n_jobs && row_off[j1 + 1] - row_off[j0] <= batch) j1++;
+            const int64_t p0 = row_off[j0], nb = row_off[j1] - p0, nj = j1 - j0;
+            ensure(d_ext_pk, (size_t)nb * (size_t)(prm.max_flank + 1)); ensure(d_ext_cs, (size_t)nj * (size_t)(prm.max_flank + 2)); ensure(d_ext_out, (size_t)(nb * max_cols));
+            be.memset(d_ext_out.p, 0, (size_t)(nb * max_cols));      // (what no kernel writes -- past column C, the rows of a dropped job -- reaches the caller as zeros)
+            be.mark("ext_trace");
+            if (prm.max_flank <= 256)
+                be.launch_wave("ext_trace", nb, ExtTrace<256>{P, d_ext_rows.p, d_ext_job.p, d_ext_off.p, prm, p0, d_ext_reach.p, d_ext_pk.p, d_ext_used.p});
+            else
+                be.launch_wave("ext_trace", nb, ExtTrace<512>{P, d_ext_rows.p, d_ext_job.p, d_ext_off.p, prm, p0, d_ext_reach.p, d_ext_pk.p, d_ext_used.p});
+            be.mark(nullptr);
+            be.mark("ext_merge");
+            be.launch_wave("ext_width", nj, ExtWidth{d_ext_off.p, prm, j0, p0, d_ext_reach.p, d_ext_pk.p, d_ext_cs.p, d_ext_cols.p});
+            be.launch_wave("ext_merge", nb, ExtMerge{P, d_ext_rows.p, d_ext_job.p, prm, j0, p0, d_ext_reach.p, d_ext_cols.p, d_ext_pk.p, d_ext_cs.p, max_cols, d_ext_out.p});
+            be.mark(nullptr);
+            bool natural = true;      // the caller's rows lie as the batch's do: one copy
+            for (int64_t j = j0; j < j1; j++) natural = natural && out_off[j] - out_off[j0] == (row_off[j] - p0) * max_cols;
+            if (natural) be.d2h(out_rows + out_off[j0], d_ext_out.p, (size_t)(nb * max_cols));
+            else {
+                stage.resize((size_t)(nb * max_cols));
+                be.d2h(stage.data(), d_ext_out.p, stage.size());
+                for (int64_t j = j0; j < j1; j++) memcpy(out_rows + out_off[j], stage.data() + (row_off[j] - p0) * max_cols, (size_t)((row_off[j + 1] - row_off[j]) * max_cols));
+            }
+            j0 = j1;
+        }
+        be.d2h_async(cols, d_ext_cols.p, 4 * (size_t)n_jobs); be.d2h_async(used, d_ext_used.p, 4 * (size_t)np);
+        be.sync();
+        collect_timing_more();
+        return 0;
+    }
+
     // The suffix array of the flagged regions of a batch (dense_kernels.h) and their rep' (after RepeatLength, which skipped them).
     // One segmented prefix-doubling sort over all of them; every round waits for its count of distinct ranks (8 bytes) -- a round
     // trip per round, on this path only.
@@ -2369,6 +2487,7 @@ public:
         if (key == "copy_kernel") { return tune_copy_kernel(be, value != 0, 0); }
         if (key == "boot_batch" && value >= 0) { boot_batch = value; return true; }
         if (key == "rec_batch" && value >= 0) { rec_batch = value; return true; }
+        if (key == "ext_batch" && value >= 0) { ext_batch = value; return true; }
         return false;
     }
 
@@ -2464,6 +2583,8 @@ private:
     Buf<int32_t> d_boot_dist, d_bt_dist, d_bt_j; Buf<double> d_bt_D, d_bt_R, d_bt_q; Buf<NjJoinRec> d_bt_joins, d_bs_mj, d_bs_rj; Buf<NjLastRec> d_bt_last;
     // the recombination scan (rec_kernels.h): transposed planes, informative flags; sites, window and matrix offsets, window numbers; matrices, phi, le
     Buf<uint64_t> d_rec_tp; Buf<uint8_t> d_rec_flag, d_rec_inc; Buf<int64_t> d_rec_sites, d_rec_woff, d_rec_moff, d_rec_wid; Buf<int32_t> d_rec_phi; Buf<uint32_t> d_rec_le;
+    // the LCB extension (ext_kernels.h): descriptors, the job of every pair, row offsets; pass bits, reaches, line maxima; paths, column starts, widths, j_r, rows
+    Buf<ExtRow> d_ext_rows; Buf<int32_t> d_ext_job, d_ext_reach, d_ext_best, d_ext_cs, d_ext_cols, d_ext_used; Buf<int64_t> d_ext_off; Buf<uint64_t> d_ext_bits; Buf<uint16_t> d_ext_pk; Buf<uint8_t> d_ext_out;
     Buf<uint64_t> d_snp_counts, d_snp_lo, d_snp_hi; Buf<uint8_t> d_snp_chunk; Buf<int64_t> d_snp_flag, d_snp_rank, d_snp_col; Buf<int32_t> d_snp_dist;      // the SNP collection (snp_kernels.h)
     Buf<uint8_t> d_ms_strand, d_ms_state, d_small8, d_o_strand; Buf<int32_t> d_ms_shift, d_ms_len, d_list, d_list2, d_j_min, d_j_max, d_o_start;
     Buf<int64_t> d_rg_start, d_rg_len, d_lay_off, d_lay_bits, d_v_row0, d_v_first, d_f_start, d_f_end, d_f_pack; Buf<RegInfo> d_rg_info; Buf<uint64_t> d_rg_count, d_once, d_twice;

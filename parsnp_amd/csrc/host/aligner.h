@@ -54,6 +54,8 @@ struct Params {
     bool recomb = false;    // [Output] recomb: the recombination scan of the core SNP columns beside them (recomb.cpp); implies snps
     int recperms = 1000, recsites = 100, recnear = 10;      // [Output] recperms, recsites, recnear: permutations, sites of a window, H
     uint64_t recseed = 1;   // [Output] recseed: the seed of the permutations
+    bool lcbext = false;    // [Output] lcbext: every printed LCB grows into its flanks, written to <stem>.xmfa.extended (extend.cpp)
+    int extmax = 256, extband = 50, extmatch = 5, extmismatch = 4, extgap = 2, extani = 95, extmin = 10;      // [Output] ext*: longest flank, band, scores, per cent, shortest kept
     bool tree = false;      // [Output] tree: the neighbour-joining tree of the SNP distances beside them (tree.cpp); implies snps
     float diag_diff = 1.0f, factor = 0.0f;
     std::string anchors, mums, anchorfile, mumfile, prefix, outdir;
@@ -583,6 +585,22 @@ bool rec_flagged(int32_t le, int32_t perms);
 std::string rec_tsv_text(const std::vector<RecWindow>& win, const int32_t* phi, const int32_t* le, int32_t perms);
 std::string rec_bed_text(const std::vector<RecWindow>& win, const int32_t* le, int32_t perms, long* flagged);
 void write_recomb(pm_session* session, const std::vector<RecColumn>& cols, const RecParams& prm, const std::string& dir, const std::string& stem);
+
+// The extension of the LCB ends into their flanks ([Output] lcbext=1; extend.cpp): the host derives the covered
+// stretches of every genome from the records' intervals, the two jobs of every printed LCB and a descriptor per row; the engine
+// aligns, cuts and merges (pm_ext_*); the host formats the records and writes <stem>.xmfa.extended.
+struct ExtSettings { int max_flank = 256, band = 50, match = 5, mismatch = 4, gap = 2, ani = 95, min_len = 10; };
+struct ExtCounts { bool on = false; long jobs = 0, kept = 0, wide = 0, bases = 0; double ms = 0; };
+extern ExtCounts ext_counts;        // what the last write_output extended (PARSNP_TIMING: ext_*, with lcbext=1 only)
+struct ExtRecord { int32_t seq; int64_t lo, hi; bool fwd; int32_t cluster; };      // a record as its header line prints it: `> seq:lo-hi +|- cluster<cluster>`
+typedef std::vector<std::vector<std::pair<int64_t, int64_t>>> ExtCovered;        // per genome the covered stretches [a, b), 0-based, ascending, merged
+void ext_limits(int* rows, int* flank, int* band);      // sequences, extmax and extband a run with lcbext=1 may have
+std::string ext_header_text(const std::vector<Genome>& genomes, int printable);
+ExtCovered ext_covered(const std::vector<std::vector<ExtRecord>>& lcbs, const std::vector<int64_t>& lens);
+pm_ext_row ext_flank(const std::string& seq, const std::vector<std::pair<int64_t, int64_t>>& cov, const ExtRecord& r, char side, int F);
+std::string ext_job_text(const std::vector<ExtRecord>& recs, const pm_ext_row* rows, const int32_t* used, const uint8_t* letters, int64_t pitch, int32_t cols, char side);
+void write_extended(pm_session* session, const std::vector<Genome>& genomes, int printable, const std::vector<std::vector<ExtRecord>>& lcbs, const ExtSettings& st,
+                    const std::string& dir, const std::string& stem, int threads);
 
 std::string reverse_complement(const std::string& s);   // Aligner::reversec, :1294-1393
 

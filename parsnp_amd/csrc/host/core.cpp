@@ -57,6 +57,14 @@ int CoreRun::open(const std::string& ini_path) {
     prm.recnear = atoi(ini.get("Output", "recnear", "10").c_str());
     prm.recseed = strtoull(ini.get("Output", "recseed", "1").c_str(), nullptr, 10);
     if (prm.recomb) prm.snps = true;    // (the scan reads the core SNP columns)
+    prm.lcbext = ini.get_bool("Output", "lcbext");
+    prm.extmax = atoi(ini.get("Output", "extmax", "256").c_str());
+    prm.extband = atoi(ini.get("Output", "extband", "50").c_str());
+    prm.extmatch = atoi(ini.get("Output", "extmatch", "5").c_str());
+    prm.extmismatch = atoi(ini.get("Output", "extmismatch", "4").c_str());
+    prm.extgap = atoi(ini.get("Output", "extgap", "2").c_str());
+    prm.extani = atoi(ini.get("Output", "extani", "95").c_str());
+    prm.extmin = atoi(ini.get("Output", "extmin", "10").c_str());
     const bool reverse_ref = ini.get_bool("Reference", "reverse");
     qfiles = (int)ini.count("Query") / 2;
 
@@ -87,6 +95,20 @@ int CoreRun::open(const std::string& ini_path) {
         if (what) {
             std::cerr << "parsnp_core: input exceeds a limit of the multi-MUM engine: recomb=1 takes at most " << rows << " sequences, 1 <= recperms <= " << perms
                       << ", " << kRecMinSites << " <= recsites <= " << sites << ", recnear >= 1 (" << what << ")" << std::endl;
+            return 5;
+        }
+    }
+
+    if (prm.lcbext) {
+        int rows = 0, flank = 0, band = 0;
+        ext_limits(&rows, &flank, &band);
+        const char* what = qfiles + 1 > rows ? "sequences" : prm.extmax < 16 || prm.extmax > flank ? "extmax" : prm.extband < 1 || prm.extband > band ? "extband"
+                           : prm.extmatch < 1 || prm.extmatch > 15 ? "extmatch" : prm.extmismatch < 0 || prm.extmismatch > 15 ? "extmismatch"
+                           : prm.extgap < 1 || prm.extgap > 15 ? "extgap" : prm.extani < 50 || prm.extani > 100 ? "extani" : prm.extmin < 1 || prm.extmin > prm.extmax ? "extmin" : nullptr;
+        if (what) {
+            std::cerr << "parsnp_core: input exceeds a limit of the multi-MUM engine: lcbext=1 takes at most " << rows << " sequences, 16 <= extmax <= " << flank
+                      << ", 1 <= extband <= " << band << ", 1 <= extmatch <= 15, 0 <= extmismatch <= 15, 1 <= extgap <= 15, 50 <= extani <= 100, 1 <= extmin <= extmax ("
+                      << what << ")" << std::endl;
             return 5;
         }
     }

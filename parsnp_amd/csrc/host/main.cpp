@@ -172,6 +172,9 @@ int main(int argc, char* argv[]) {
             if (rec_counts.on)      // (recomb=1 only)
                 fprintf(f, ", \"rec_sites\": %ld, \"rec_windows\": %ld, \"rec_flagged\": %ld, \"rec_ms\": %.3f", rec_counts.sites, rec_counts.windows,
                         rec_counts.flagged, rec_counts.ms);
+            if (ext_counts.on)      // (lcbext=1 only)
+                fprintf(f, ", \"ext_jobs\": %ld, \"ext_kept\": %ld, \"ext_wide\": %ld, \"ext_bases\": %ld, \"ext_ms\": %.3f", ext_counts.jobs, ext_counts.kept,
+                        ext_counts.wide, ext_counts.bases, ext_counts.ms);
             fprintf(f, "}\n");
             fclose(f);
         }

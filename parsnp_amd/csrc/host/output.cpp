@@ -919,6 +919,24 @@ void write_output(Aligner& a, const std::string& stem, bool* gap_note) {
     rec_counts = RecCounts();
     const RecParams rec_prm{prm.recperms, prm.recseed, prm.recsites, prm.recnear};
     if (snp) { snp->finish(a.genomes, dir, stem, prm.tree, prm.bootstrap, prm.bootseed, prm.recomb ? &rec_prm : nullptr); lap("snp columns"); }
+    ext_counts = ExtCounts();
+    if (prm.lcbext) {      // the intervals of the records as their header lines print them: extend.cpp grows the LCBs from them
+        vector<vector<ExtRecord>> ext_lcbs;
+        for (size_t z = 0; z < (size_t)nl; z++) {
+            if (!printed[z]) continue;
+            const Lcb& ct = trimmed[z];
+            const Mum& first = a.pool[(size_t)ct.mums.front()];
+            const Mum& lastm = a.pool[(size_t)ct.mums.back()];
+            vector<ExtRecord> recs;
+            for (size_t i = 0; i < n; i++)
+                recs.push_back(first.fwd[i] ? ExtRecord{(int32_t)i + 1, (int64_t)ct.start[i] + 1, (int64_t)ct.end[i], true, (int32_t)z + 1}
+                                            : ExtRecord{(int32_t)i + 1, (int64_t)lastm.start[i] + 1, (int64_t)first.end(i), false, (int32_t)z + 1});
+            ext_lcbs.push_back(std::move(recs));
+        }
+        const ExtSettings ext_st{prm.extmax, prm.extband, prm.extmatch, prm.extmismatch, prm.extgap, prm.extani, prm.extmin};
+        write_extended(a.session(), a.genomes, printable, ext_lcbs, ext_st, dir, stem, threads);
+        lap("lcb extension");
+    }
     // ---- log (:1082-1190); stream flags are sticky exactly as in the reference
     log << "Number of sequences analyzed:" << setiosflags(ios::fixed) << setprecision(1) << setw(10) << n << endl << endl;
     for (size_t i = 0; i < n; i++) {

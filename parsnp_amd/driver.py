@@ -51,13 +51,16 @@ def driver_order(paths):
     return out
 
 
-def ini_text(ref, queries, outdir, snps=None, tree=None, bootstrap=None, bootseed=None, recomb=None, recperms=None, recseed=None, recsites=None, recnear=None, **kw):
+def ini_text(ref, queries, outdir, snps=None, tree=None, bootstrap=None, bootseed=None, recomb=None, recperms=None, recseed=None, recsites=None, recnear=None,
+             lcbext=None, extmax=None, extband=None, extmatch=None, extmismatch=None, extgap=None, extani=None, extmin=None, **kw):
     """snps=1: `snps=1` under [Output] (core SNP columns and SNP distances beside the XMFA: read_snps; the reference ignores the
     key).  tree=1: `tree=1` there (it implies snps=1: the neighbour-joining tree of the SNP distances, read_tree).  bootstrap=B:
     `bootstrap=B` there (it implies tree=1: the tree once more with the support of B bootstrap replicates on its branches,
     read_boot_tree); bootseed=S: the seed of the replicates (default 1).  recomb=1: `recomb=1` there (it implies snps=1: the
     recombination scan of the core SNP columns, read_rec), with recperms=P permutations (default 1000), recseed=S (1), recsites=K
-    sites a window (100) and recnear=H (10).  Without the arguments the text is the reference driver's, byte for byte."""
+    sites a window (100) and recnear=H (10).  lcbext=1: `lcbext=1` there (every printed LCB grows into its flanks: read_extended), with
+    extmax=F the longest flank (default 256), extband=W the band's half-width (50), extmatch, extmismatch, extgap the scores (5, 4,
+    2), extani the per cent a row must keep (95) and extmin the shortest kept extension (10).  Without the arguments the text is the reference driver's, byte for byte."""
     p = dict(DEFAULTS, **kw)
     files = "".join("file%d=%s\nreverse%d=0\n" % (i, q, i) for i, q in enumerate(queries, 1))
     text = _TEMPLATE.format(ref=ref, files=files, outdir=outdir, **p)
@@ -69,7 +72,9 @@ def ini_text(ref, queries, outdir, snps=None, tree=None, bootstrap=None, bootsee
         text += "bootstrap=%d\n" % int(bootstrap)
     if bootseed is not None:
         text += "bootseed=%d\n" % int(bootseed)
-    for key, value in (("recomb", recomb), ("recperms", recperms), ("recseed", recseed), ("recsites", recsites), ("recnear", recnear)):
+    for key, value in (("recomb", recomb), ("recperms", recperms), ("recseed", recseed), ("recsites", recsites), ("recnear", recnear), ("lcbext", lcbext),
+                       ("extmax", extmax), ("extband", extband), ("extmatch", extmatch), ("extmismatch", extmismatch), ("extgap", extgap), ("extani", extani),
+                       ("extmin", extmin)):
         if value is not None:
             text += "%s=%d\n" % (key, int(value))
     return text
@@ -150,3 +155,25 @@ def read_rec(outdir, stem="parsnpAligner"):
     bed = open(os.path.join(outdir, stem + ".rec")).read().split("\n")
     assert bed[-1] == ""
     return rows, bed[:-1]
+
+
+def read_extended(outdir, stem="parsnpAligner"):
+    """the file a run with lcbext=1 leaves beside the XMFA -> (header lines, [(cluster, side, [(seq, lo, hi, strand, letters)])]): a
+    job per kept extension in the file's order, side "L" or "R", a record per row with its 1-based inclusive interval (0, 0 for a row
+    that contributes no base)"""
+    import re
+    head, jobs, recs = [], [], []
+    for line in open(os.path.join(outdir, stem + ".xmfa.extended")).read().split("\n")[:-1]:
+        if line.startswith("#"):
+            head.append(line)
+        elif line.startswith(">"):
+            m = re.fullmatch(r"> (\d+):(\d+)-(\d+) ([+-]) cluster(\d+) ([LR])", line)
+            recs.append([int(m.group(1)), int(m.group(2)), int(m.group(3)), m.group(4), ""])
+            key = (int(m.group(5)), m.group(6))
+        elif line == "=":
+            jobs.append((key[0], key[1], [tuple(r) for r in recs]))
+            recs = []
+        else:
+            recs[-1][4] += line
+    assert not recs
+    return head, jobs
