@@ -523,6 +523,7 @@ extern UnalignCounts unalign_counts;
 struct SnpCounts { bool on = false; long columns = 0, invariant = 0, core = 0, other = 0; double h2d_bytes = 0, scan_ms = 0, dist_ms = 0; };
 extern SnpCounts snp_counts;      // what the last write_output collected (PARSNP_TIMING: snp_*, with snps=1 only)
 int snp_max_rows();               // sequences a run with snps=1 may have
+struct RecColumn { int32_t cluster; int64_t column, ref_pos; };      // a core SNP column as <stem>.snps.tsv prints it
 class SnpCollector {
 public:
     SnpCollector(pm_session* session, size_t n_rows, int threads);
@@ -536,12 +537,11 @@ public:
     size_t pitch() const { return pitch_; }
     uint8_t* reserve(size_t width);
     long commit(int cluster, long c0, size_t width, const int64_t* ref_pos, int64_t ref_base);
-    // the three files beside the XMFA, the console line, snp_counts
-    // (tree: then the neighbour-joining tree of the distances, which are still on the device -- tree.cpp)
-    // (bootstrap > 0: then the tree once more with the support of bootstrap replicates on its branches)
-    // (rec: then the recombination scan of the columns, which are still on the device -- recomb.cpp)
-    void finish(const std::vector<Genome>& genomes, const std::string& dir, const std::string& stem, bool tree = false, int bootstrap = 0, uint64_t bootseed = 1,
-                const struct RecParams* rec = nullptr);
+    // the three files beside the XMFA and snp_counts.  Handed back is what the steps after it need (the columns and the distances are
+    // still on the device, too): the names, the n x n distances and, when asked for, every core SNP column as the .snps.tsv prints it
+    struct Result { std::vector<std::string> names; std::vector<int32_t> dist; std::vector<RecColumn> columns; };
+    Result finish(const std::vector<Genome>& genomes, const std::string& dir, const std::string& stem, bool want_columns);
+    void report() const;      // the console line, from snp_counts (the writer prints it after those steps' lines, as ever)
 
 private:
     struct Entry { int64_t first; int32_t cluster; int32_t width; int64_t c0; };      // columns [first, first + width) of all columns handed over
@@ -575,7 +575,6 @@ struct RecParams { int perms = 1000; uint64_t seed = 1; int sites = 100; int nea
 struct RecCounts { bool on = false; long sites = 0, windows = 0, flagged = 0; double ms = 0; };
 extern RecCounts rec_counts;        // what the last write_output scanned (PARSNP_TIMING: rec_*, with recomb=1 only)
 constexpr size_t kRecMinSites = 16; // an LCB with fewer informative sites has no window
-struct RecColumn { int32_t cluster; int64_t column, ref_pos; };      // a core SNP column as <stem>.snps.tsv prints it
 struct RecWindow { int32_t cluster; int64_t first_column, last_column, first_ref, last_ref; int32_t sites; };
 void rec_limits(int* rows, int* sites, int* perms);      // sequences, recsites and recperms a run with recomb=1 may have
 std::vector<size_t> rec_window_starts(size_t m, size_t K);

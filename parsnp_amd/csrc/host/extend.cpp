@@ -12,6 +12,7 @@
 #include <iostream>
 
 #include "aligner.h"
+#include "engine_step.h"
 
 // Weak, like the pm_rec_* calls: a provider of the ABI without them still links; lcbext=1 then ends the run.
 extern "C" int pm_ext_limits(int* max_rows, int* max_flank, int* max_band) __attribute__((weak));
@@ -28,7 +29,7 @@ void ext_limits(int* rows, int* flank, int* band) {
     if (pm_ext_limits) (void)pm_ext_limits(rows, flank, band);
 }
 
-// the header lines of the XMFA (output.cpp writes the same)
+// the header lines of the XMFA (output.cpp writes its own with it)
 std::string ext_header_text(const std::vector<Genome>& genomes, int printable) {
     std::string t = "#FormatVersion Mauve\n#SequenceCount " + std::to_string(genomes.size()) + "\n";
     for (size_t i = 0; i < genomes.size(); i++) {
@@ -117,13 +118,8 @@ void write_extended(pm_session* session, const std::vector<Genome>& genomes, int
     }
     double ms = 0;
     auto step = [&](int rc, const char* what) {
-        if (rc != PM_OK) {
-            std::cerr << "parsnp_core: cannot extend the LCBs (" << what << "): " << pm_last_error() << std::endl;
-            exit(rc == PM_ELIMIT ? 5 : 1);
-        }
-        int c = 64; const char* tn[64]; float tms[64];
-        if (pm_last_timing(session, &c, tn, tms) == PM_OK)
-            for (int i = 0; i < c; i++) if (!strncmp(tn[i], "ext_", 4)) ms += tms[i];
+        engine_check(rc, std::string("cannot extend the LCBs (") + what + ")");
+        ms += phase_ms(session, "ext_", true);
     };
     std::vector<int64_t> lens;
     for (const Genome& g : genomes) lens.push_back((int64_t)g.seq.size());

@@ -13,6 +13,7 @@
 #include <iostream>
 
 #include "aligner.h"
+#include "engine_step.h"
 
 // Weak, like the pm_nj_* calls: a provider of the ABI without them still links; recomb=1 then ends the run.
 extern "C" int pm_rec_limits(int* max_rows, int* max_window_sites, int* max_perms) __attribute__((weak));
@@ -104,13 +105,8 @@ void write_recomb(pm_session* session, const std::vector<RecColumn>& cols, const
     }
     double ms = 0;
     auto step = [&](int rc, const char* what) {
-        if (rc != PM_OK) {
-            std::cerr << "parsnp_core: cannot scan for recombination (" << what << "): " << pm_last_error() << std::endl;
-            exit(rc == PM_ELIMIT ? 5 : 1);
-        }
-        int c = 64; const char* tn[64]; float tms[64];
-        if (pm_last_timing(session, &c, tn, tms) == PM_OK)
-            for (int i = 0; i < c; i++) if (!strncmp(tn[i], "rec_", 4)) ms += tms[i];
+        engine_check(rc, std::string("cannot scan for recombination (") + what + ")");
+        ms += phase_ms(session, "rec_", true);
     };
     std::vector<uint8_t> informative(cols.size());
     int64_t n_inf = 0;

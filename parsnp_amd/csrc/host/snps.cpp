@@ -17,6 +17,7 @@
 #include <iostream>
 
 #include "aligner.h"
+#include "engine_step.h"
 #include "hooks.h"
 
 // Weak: a provider of the ABI without them (the CPU checker of the test builds) still links; snps=1 then ends the run.
@@ -31,10 +32,6 @@ SnpCounts snp_counts;
 
 namespace {
 constexpr size_t kStageBytes = (size_t)32 << 20;      // the staging matrix: 16 K columns of 2 000 rows
-[[noreturn]] void snp_fatal(const std::string& what, int rc) {
-    std::cerr << "parsnp_core: " << what << ": " << pm_last_error() << std::endl;
-    exit(rc == PM_ELIMIT ? 5 : 1);
-}
 }  // namespace
 
 int snp_max_rows() {
@@ -48,8 +45,7 @@ SnpCollector::SnpCollector(pm_session* session, size_t n_rows, int threads) : se
         std::cerr << "parsnp_core: this provider of the engine's ABI cannot collect SNP columns (snps=1)" << std::endl;
         exit(1);
     }
-    const int rc = pm_snp_begin(session_, (int32_t)n_rows);
-    if (rc != PM_OK) snp_fatal("cannot start the SNP collection", rc);
+    engine_check(pm_snp_begin(session_, (int32_t)n_rows), "cannot start the SNP collection");
     pitch_ = std::min<size_t>(std::max<size_t>(kStageBytes / n_, 1024), (size_t)1 << 20);
     if (const char* v = test_hook("PARSNP_SNP_STAGE_COLUMNS")) pitch_ = (size_t)std::max(1L, atol(v));      // test hook: a staging matrix of a few columns
     stage_.resize(n_ * pitch_);
@@ -86,34 +82,25 @@ void SnpCollector::flush() {
     if (!used_) return;
     uint64_t h0 = 0, h1 = 0;
     (void)pm_session_traffic(session_, &h0, nullptr);
-    const int rc = pm_snp_add(session_, (int64_t)used_, (int64_t)pitch_, stage_.data(), &counts_);
-    if (rc != PM_OK) snp_fatal("cannot classify the columns", rc);
+    engine_check(pm_snp_add(session_, (int64_t)used_, (int64_t)pitch_, stage_.data(), &counts_), "cannot classify the columns");
     (void)pm_session_traffic(session_, &h1, nullptr);
     h2d_bytes_ += (double)(h1 - h0);
-    int cnt = 64; const char* names[64]; float ms[64];
-    if (pm_last_timing(session_, &cnt, names, ms) == PM_OK)
-        for (int i = 0; i < cnt; i++) if (!strncmp(names[i], "snp_", 4)) scan_ms_ += ms[i];
+    scan_ms_ += phase_ms(session_, "snp_", true);
     used_ = 0;
 }
 
-void SnpCollector::finish(const std::vector<Genome>& genomes, const std::string& dir, const std::string& stem, bool tree, int bootstrap, uint64_t bootseed,
-                          const RecParams* rec) {
+SnpCollector::Result SnpCollector::finish(const std::vector<Genome>& genomes, const std::string& dir, const std::string& stem, bool want_columns) {
     flush();
     const size_t v = (size_t)counts_.core_snps;
     std::vector<int64_t> col(v);
     std::vector<uint8_t> letters(n_ * v);
-    std::vector<int32_t> dist(n_ * n_);
-    std::vector<RecColumn> rec_cols;      // (recomb=1: what the .snps.tsv says of every core SNP column)
-    int rc = pm_snp_columns(session_, col.data(), letters.data());
-    if (rc != PM_OK) snp_fatal("cannot fetch the SNP columns", rc);
-    rc = pm_snp_distances(session_, dist.data());
-    if (rc != PM_OK) snp_fatal("cannot compute the SNP distances", rc);
-    double dist_ms = 0;
-    {
-        int cnt = 64; const char* names[64]; float ms[64];
-        if (v && pm_last_timing(session_, &cnt, names, ms) == PM_OK)
-            for (int i = 0; i < cnt; i++) if (!strcmp(names[i], "snp_dist")) dist_ms += ms[i];
-    }
+    Result res;
+    std::vector<int32_t>& dist = res.dist;
+    dist.resize(n_ * n_);
+    for (size_t i = 0; i < n_; i++) res.names.push_back(genomes[i].fname);
+    engine_check(pm_snp_columns(session_, col.data(), letters.data()), "cannot fetch the SNP columns");
+    engine_check(pm_snp_distances(session_, dist.data()), "cannot compute the SNP distances");
+    const double dist_ms = v ? phase_ms(session_, "snp_dist", false) : 0;
     {
         std::ofstream mfa((dir + stem + ".snps.mfa").c_str(), std::ios::binary);
         for (size_t i = 0; i < n_; i++) {
@@ -125,13 +112,13 @@ void SnpCollector::finish(const std::vector<Genome>& genomes, const std::string&
     {
         std::ofstream tsv((dir + stem + ".snps.tsv").c_str(), std::ios::binary);
         tsv << "cluster\tcolumn\tref_pos\n";
-        if (rec) rec_cols.reserve(v);
+        if (want_columns) res.columns.reserve(v);
         size_t e = 0;      // (col ascends: the entries are walked once)
         for (size_t k = 0; k < v; k++) {
             while (e + 1 < entries_.size() && entries_[e + 1].first <= col[k]) e++;
             const Entry& en = entries_[e];
             tsv << en.cluster << '\t' << en.c0 + (col[k] - en.first) << '\t' << ref_pos_[(size_t)col[k]] << '\n';
-            if (rec) rec_cols.push_back(RecColumn{en.cluster, en.c0 + (col[k] - en.first), ref_pos_[(size_t)col[k]]});
+            if (want_columns) res.columns.push_back(RecColumn{en.cluster, en.c0 + (col[k] - en.first), ref_pos_[(size_t)col[k]]});
         }
     }
     {
@@ -147,16 +134,14 @@ void SnpCollector::finish(const std::vector<Genome>& genomes, const std::string&
             out << line;
         }
     }
-    if (tree) {      // (the last engine call was pm_snp_distances: its matrix is what the tree is built over)
-        std::vector<std::string> names;
-        for (size_t i = 0; i < n_; i++) names.push_back(genomes[i].fname);
-        write_tree(session_, names, dist.data(), dir, stem, bootstrap, bootseed);
-    }
-    if (rec) write_recomb(session_, rec_cols, *rec, dir, stem);      // (the collection is still on the device; the tree does not touch it)
     snp_counts.on = true;
     snp_counts.columns = (long)counts_.columns + invariant_; snp_counts.invariant = (long)counts_.core_invariant + invariant_;
     snp_counts.core = (long)counts_.core_snps; snp_counts.other = (long)counts_.other;
     snp_counts.h2d_bytes = h2d_bytes_; snp_counts.scan_ms = scan_ms_; snp_counts.dist_ms = dist_ms;
+    return res;
+}
+
+void SnpCollector::report() const {
     std::cerr << "SNP columns: " << snp_counts.columns << " columns, " << snp_counts.invariant << " core invariant, " << snp_counts.core << " core SNPs, "
               << snp_counts.other << " other" << std::endl;
 }

@@ -21,6 +21,7 @@
 #include <iostream>
 
 #include "aligner.h"
+#include "engine_step.h"
 
 // Weak, like the pm_snp_* calls: a provider of the ABI without them still links; tree=1 then ends the run.
 extern "C" int pm_nj_limits(int* max_rows) __attribute__((weak));
@@ -124,14 +125,8 @@ void write_tree(pm_session* session, const std::vector<std::string>& names, cons
         std::vector<pm_nj_join> joins(n - 3 ? n - 3 : 1);
         pm_nj_last last;
         memset(&last, 0, sizeof last);
-        const int rc = pm_nj_tree(session, (int32_t)n, nullptr, joins.data(), &last);
-        if (rc != PM_OK) {
-            std::cerr << "parsnp_core: cannot build the neighbour-joining tree: " << pm_last_error() << std::endl;
-            exit(rc == PM_ELIMIT ? 5 : 1);
-        }
-        int cnt = 64; const char* tn[64]; float tms[64];
-        if (pm_last_timing(session, &cnt, tn, tms) == PM_OK)
-            for (int i = 0; i < cnt; i++) if (!strcmp(tn[i], "nj")) ms += tms[i];
+        engine_check(pm_nj_tree(session, (int32_t)n, nullptr, joins.data(), &last), "cannot build the neighbour-joining tree");
+        ms = phase_ms(session, "nj", false);
         joins_made = (long)n - 3;
         text = nj_newick(names, joins.data(), last);
         if (bootstrap > 0 && n > 3) {      // (three leaves have no internal branch: no label, no call)
@@ -141,13 +136,8 @@ void write_tree(pm_session* session, const std::vector<std::string>& names, cons
             }
             std::vector<int32_t> support(n - 3);
             auto step = [&](int rc, const char* what) {
-                if (rc != PM_OK) {
-                    std::cerr << "parsnp_core: cannot bootstrap the tree (" << what << "): " << pm_last_error() << std::endl;
-                    exit(rc == PM_ELIMIT ? 5 : 1);
-                }
-                int c = 64; const char* tn2[64]; float tms2[64];
-                if (pm_last_timing(session, &c, tn2, tms2) == PM_OK)
-                    for (int i = 0; i < c; i++) if (!strncmp(tn2[i], "boot_", 5)) boot_ms += tms2[i];
+                engine_check(rc, std::string("cannot bootstrap the tree (") + what + ")");
+                boot_ms += phase_ms(session, "boot_", true);
             };
             step(pm_boot_distances(session, bootstrap, bootseed, nullptr, 0, nullptr, nullptr), "distances");
             step(pm_nj_trees(session, (int32_t)n, bootstrap, nullptr, nullptr, nullptr), "trees");
